@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- DEGA encode throughput on MI355X (BASELINE.json metric: Msamples/s DEGA encode (int32)).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one rank per
 GPU; RANK / LOCAL_RANK / WORLD_SIZE come from the environment and WORLD_SIZE must equal N), or started plainly, in
@@ -13,12 +13,20 @@ synthetic meter channels that is already resident in HBM: BASELINE.json configs[
 samples per GPU, [T][C] layout (22.6 GB), generated on the device.  Channels are independent, so N GPUs
 = N disjoint channel ranges, no data-path collective ("scaling": "weak": per-GPU work is fixed).
 
-One JSON line on rank 0: throughput, the roofline of the encode kernel (HBM; algorithmic bytes = 4 B read per sample +
-the stream bytes written, over the kernel's hipEvent time on its own stream; beside it the instruction-issue bound the
-kernel actually runs against), the CPU baseline (the reference itself, oracle/_ref, when it was built -- else our C
-port of it -- timed single threaded on a bounded sample of the same channels, whose GPU streams are also compared bit
-for bit), the PCIe-inclusive host-pointer path (`end_to_end`), and -- after the timed region, N = 1 only -- `extra`:
-the other BASELINE configs at full size (cfg3 short series, cfg4 LZMH, one GPU's share of cfg5)."""
+One JSON line on rank 0: throughput, `ms_per_step` (the wall time of one timed step) and the roofline of the encode kernel
+(HBM; algorithmic bytes = 4 B read per sample + the stream bytes written, over the kernel's hipEvent time on its own
+stream).  A plain run does only that: set up, warm up, time the steps, write the outputs (--dump-outputs DIR) and print
+the line.  With --full the line also carries, after the timed region: the bit-exact round trip at full size (decode on
+the device, compare), the CPU baseline (the reference itself, oracle/_ref, when it was built -- else our C port of it --
+timed single threaded on a bounded sample of the same channels, whose GPU streams are also compared bit for bit; beside
+it the instruction-issue bound the kernel actually runs against, and the same CPU code on all cores), the
+PCIe-inclusive host-pointer path (`end_to_end`), and -- N = 1 only -- `extra`: the other BASELINE configs at full size
+(cfg3 short series, cfg4 LZMH, one GPU's share of cfg5).
+
+--dump-outputs DIR writes what the timed path handed its caller in the last timed step (rank 0's channels): every
+channel's stream length in bits and status, and the stream bytes of a fixed, seeded sample of channels, as .npy files
+(float64 / float32, well under 64 MB).  The inputs are generated from a fixed seed, so two builds run with the same
+arguments can be compared output for output."""
 import argparse
 import json
 import os
@@ -38,6 +46,35 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.
 ISSUE_INSTR_PER_SYMBOL = 743.0 / 32.0
 ISSUE_CYCLES_PER_INSTR = 4.3   # the mix of 4- and 8-byte encodings of the word path
 SHADER_CLOCK_HZ = 2.25e9
+DUMP_ROWS = 24               # --dump-outputs: stream rows of the seeded channel sample
+DUMP_ROW_BYTES = 40 << 20    # ... at most this many bytes of them as float32 (the leading bytes of each row)
+DUMP_MAX_CHANNELS = 1 << 20  # ... and the lengths / statuses of at most this many channels (a seeded sample beyond it)
+
+
+def dump_outputs(dump_dir, out, bits, err):
+    """Write what one call of the timed path returned -- out [C, cap] stream slabs, bits [C], err [C] -- as .npy files:
+    bits.npy and err.npy (float64, every channel), stream_bytes.npy (float32 [rows, width]: the leading bytes of the
+    slab rows of a seeded sample of channels) and stream_channels.npy (float64: which channels those rows are)."""
+    import numpy as np
+    import torch
+    os.makedirs(dump_dir, exist_ok=True)
+    C_, cap = out.shape
+    rng = np.random.default_rng(0)
+    chans = np.arange(C_) if C_ <= DUMP_MAX_CHANNELS else np.sort(rng.choice(C_, DUMP_MAX_CHANNELS, replace=False))
+    rows = np.sort(rng.choice(C_, min(DUMP_ROWS, C_), replace=False))
+    width = min(cap, DUMP_ROW_BYTES // (4 * rows.size))
+    ci = torch.from_numpy(chans).to(out.device)
+    ri = torch.from_numpy(rows).to(out.device)
+    arrays = {
+        "bits": bits.index_select(0, ci).double(),
+        "err": err.index_select(0, ci).double(),
+        "stream_bytes": out.index_select(0, ri)[:, :width].float(),
+        "stream_channels": ri.double(),
+    }
+    if chans.size != C_:
+        arrays["channels"] = ci.double()
+    for name, t in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), t.cpu().numpy())
 
 
 def _cpu_encode_columns(job):
@@ -326,6 +363,8 @@ def run_dega(env, args):
     ctx.profile(False)
     n_launch, kernel_ms = ctx.profile_read(0)
     elapsed = env.reduce_max([elapsed])[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, bits, err)
 
     # bit-exact round trip at full size (the size-independent property of the metric): decode every stream on the
     # device and compare with the input on the device
@@ -459,6 +498,9 @@ def run_roundtrip(env, args):
     env.barrier()
     elapsed = time.perf_counter() - t0
     elapsed, enc_ms, dec_ms, bad = env.reduce_max([elapsed, enc_ms, dec_ms, 0.0 if ok else 1.0])
+    if args.dump_outputs and rank == 0 and args.steps > 0:  # the last batch of the last step: what the buffers hold
+        n = C_ - (nbatch - 1) * B
+        dump_outputs(args.dump_outputs, out[:n], bits[:n], err[:n])
     res = None
     if rank == 0:
         kernel_s = (enc_ms + dec_ms) * 1e-3
@@ -586,6 +628,8 @@ def run_lzmh(env, args):
     ctx.profile(False)
     n_launch, kernel_ms = ctx.profile_read(2)
     elapsed = env.reduce_max([elapsed])[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, bits, err)
     in_bytes = int(lens.sum().item())
     tot = torch.tensor([in_bytes], dtype=torch.int64, device=dev)
     if world > 1:
@@ -650,6 +694,7 @@ def run_lzmh(env, args):
 def extras(env, args):
     """The other BASELINE configs at full size, after the timed region (N = 1): sub-records with their own roofline."""
     out = {}
+    args = argparse.Namespace(**dict(vars(args), dump_outputs=None))  # the headline's outputs are the ones dumped
     a = argparse.Namespace(**vars(args))
     # configs[2]: 1 Mi channels x 96 samples (15-min data, S = 300): encode with its round trip
     a.channels, a.samples, a.step_size, a.steps, a.warmup, a.cpu_channels, a.end_to_end_channels, a.no_round_trip = 1048576, 96, 300, 5, 1, 0, 0, False
@@ -684,22 +729,30 @@ def main():
     ap.add_argument("--samples", type=int, default=86400, help="samples per channel")
     ap.add_argument("--step-size", type=int, default=50, help="S of the synthetic random walk")
     ap.add_argument("--cap-bytes-per-sample", type=float, default=4.0, help="slab bytes per sample per channel")
-    ap.add_argument("--cpu-channels", type=int, default=256, help="channels of the CPU baseline sample (0 = skip)")
-    ap.add_argument("--no-round-trip", action="store_true", help="skip the decode + compare after the timed region")
-    ap.add_argument("--no-all-cores", action="store_true", help="skip the process-parallel CPU baseline")
-    ap.add_argument("--no-extras", action="store_true", help="skip the cfg3 / cfg4 / cfg5-share sub-records after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also check and measure everything beyond the headline: round trip, CPU baselines, "
+                         "host-pointer and group paths, the other BASELINE configs (the options below marked --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (stream lengths and statuses, a seeded sample of stream bytes) as .npy files to DIR")
+    ap.add_argument("--cpu-channels", type=int, default=256, help="--full: channels of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--no-round-trip", action="store_true", help="--full: skip the decode + compare after the timed region")
+    ap.add_argument("--no-all-cores", action="store_true", help="--full: skip the process-parallel CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the cfg3 / cfg4 / cfg5-share sub-records after the timed region")
     ap.add_argument("--end-to-end-channels", type=int, default=8192,
-                    help="channels of the host-pointer (PCIe-inclusive) measurement after the timed region (0 = skip)")
+                    help="--full: channels of the host-pointer (PCIe-inclusive) measurement after the timed region (0 = skip)")
     ap.add_argument("--lzmh-input", choices=("ascii", "raw"), default="ascii",
                     help="lzmh workload: the channels as ASCII '%%d.%%02d\\n' lines (the codec's domain) or as raw big-endian int32 bytes")
     ap.add_argument("--workload", choices=("dega", "lzmh", "roundtrip"), default="dega",
                     help="dega = BASELINE configs[1] (the headline metric); lzmh = configs[3], the same channels as ASCII lines through LZMH; "
                          "roundtrip = one GPU's share of configs[4]: --channels streamed in batches of --batch-channels, encode + decode + compare")
-    ap.add_argument("--lzmh-end-to-end-channels", type=int, default=0, help="lzmh workload: channels of the host-pointer (PCIe-inclusive) measurement (0 = skip)")
+    ap.add_argument("--lzmh-end-to-end-channels", type=int, default=0, help="--full, lzmh workload: channels of the host-pointer (PCIe-inclusive) measurement (0 = skip)")
     ap.add_argument("--batch-channels", type=int, default=131072, help="roundtrip workload: channels per batch (x + slabs + decoded samples must fit HBM)")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be at least 1")
+    if not args.full:  # a plain run: set up, warm up, time the steps, dump the outputs, print the line
+        args.no_round_trip, args.no_all_cores, args.no_extras = True, True, True
+        args.cpu_channels = args.end_to_end_channels = args.lzmh_end_to_end_channels = 0
     spawn_ranks_if_needed(args)  # does not return in the launching process
 
     pool, ncores = None, 0

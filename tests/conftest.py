@@ -7,6 +7,10 @@ import os
 import sys
 
 import pytest
+# torch first, before any test loads libdega_hip.so: torch carries its own HIP runtime, and libtorch_hip asks for it as
+# libamdhip64.so while libdega_hip.so asks for libamdhip64.so.7.  Loaded after torch, our library binds to torch's copy
+# (same soname); loaded before it, the process ends up with two HIP runtimes, and contexts on the device then fail.
+import torch  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

@@ -19,6 +19,9 @@ Fixtures are data only (inputs + the reference's outputs):
                        `encode diff valuesize=n # encode seg valuesize=n # encode bac [adaptive]`, error channels included
   lzmh.json / lzmh.npz the reference's `encode lzmh` of the test file (size, bits, sha256) and of small byte strings
                        (meter CSV text, digits, binary, periodic; lengths around the 403-byte ring size)
+  dega_random.json     the reference's results (status, bits, sha256) on the seeded random channels and decoder garbage of
+                       tests/test_oracle_golden.py (the inputs are generated there, from their seeds)
+  lzmh_random.json     the same for the seeded random and long byte strings of tests/test_lzmh_oracle.py
 """
 import gzip
 import hashlib
@@ -413,6 +416,26 @@ def lzmh():
           "not round-tripping:", [k for k, v in meta.items() if k != "testfile" and not v["decodes_to_input"]])
 
 
+def random_records():
+    """The compiled reference on the seeded random inputs of two test modules, which define the inputs and the records."""
+    import importlib.util
+    mods = {}
+    for name in ("test_oracle_golden", "test_lzmh_oracle"):
+        spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
+        mods[name] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mods[name])
+    dega = mods["test_oracle_golden"].reference_records()
+    with open(os.path.join(HERE, "dega_random.json"), "w") as f:
+        json.dump(dega, f)
+    m = mods["test_lzmh_oracle"]
+    lz = {"random_inputs": [m.reference_record(d, g) for d, g in m.random_inputs()],
+          "long_inputs": [m.reference_record(d) for d in m.long_inputs()]}
+    with open(os.path.join(HERE, "lzmh_random.json"), "w") as f:
+        json.dump(lz, f)
+    print("random records: dega %d channel records, %d garbage records; lzmh %d + %d"
+          % (len(dega["channels"]), len(dega["garbage"]), len(lz["random_inputs"]), len(lz["long_inputs"])))
+
+
 if __name__ == "__main__":
     assert orc.have_ref() and os.path.exists(orc.REF_CLI), "build oracle/_ref first: make -C oracle"
     testfile()
@@ -424,6 +447,9 @@ if __name__ == "__main__":
     if only == ["floats_vs"]:
         floats_vs()
         sys.exit(0)
+    if only == ["random"]:
+        random_records()
+        sys.exit(0)
     if only == ["valuesizes"]:
         valuesizes()
         valuesizes64()
@@ -434,3 +460,4 @@ if __name__ == "__main__":
     valuesizes()
     valuesizes64()
     lzmh()
+    random_records()

@@ -1,5 +1,5 @@
 """The LZMH restatement (oracle/lzmh_oracle.c) against the fixtures made from the compiled reference
-(tests/golden/lzmh.json, lzmh.npz) and, where oracle/_ref exists, against the compiled reference on random inputs."""
+(tests/golden/lzmh.json, lzmh.npz, lzmh_random.json) and, where oracle/_ref exists, against the compiled reference itself."""
 import gzip
 import hashlib
 import json
@@ -56,8 +56,12 @@ def test_lzmh_rejects_partial_byte():
     assert orc.stage("lzmh", True, b"\xff\x80", 9)[0] == orc.ERROR_LIBRARY_CALL
 
 
-@pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
-def test_lzmh_restatement_equals_compiled_reference_on_random_inputs():
+def sha(b):
+    return hashlib.sha256(b).hexdigest()
+
+
+def random_inputs():
+    """The seeded random byte strings of the comparison with the compiled reference: (data, 40 garbage bytes) per case."""
     rng = np.random.default_rng(3)
     for it in range(300):
         kind = it % 5
@@ -72,28 +76,58 @@ def test_lzmh_restatement_equals_compiled_reference_on_random_inputs():
             data = bytes(rng.integers(0, 3, L, dtype=np.uint8))
         else:
             data = (b"abcabcabd" * (L // 9 + 1))[:L]
-        a = orc.stage("lzmh", True, data, 8 * len(data))
-        r = orc.ref_run_chain(data, 8 * len(data), ["encode lzmh"])
-        assert a == (r[0], r[1], r[2]), (it, kind, L)
-        d = orc.stage("lzmh", False, a[1], a[2])
-        dr = orc.ref_run_chain(a[1], a[2], ["decode lzmh"])
-        assert d == (dr[0], dr[1], dr[2]), (it, kind, L)
-        # garbage into the decoder: the reference reads never-written list symbols there (lzmh.c:395, :434), so only
-        # the status and the length are defined
-        g = bytes(rng.integers(0, 256, 40, dtype=np.uint8))
-        d = orc.stage("lzmh", False, g, 8 * len(g))
-        dr = orc.ref_run_chain(g, 8 * len(g), ["decode lzmh"])
-        assert (d[0], d[2]) == (dr[0], dr[2]), it
+        yield data, bytes(rng.integers(0, 256, 40, dtype=np.uint8))
 
 
-@pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
-def test_lzmh_restatement_equals_compiled_reference_on_long_inputs():
-    """Count saturation at 65 535 (lzmh.c:304) and back-to-back 274-byte matches: beyond what the short fixtures reach."""
+def long_inputs():
     rng = np.random.default_rng(42)
-    for data in (bytes(rng.integers(48, 58, 1_500_000, dtype=np.uint8)), bytes(600_000)):
+    return [bytes(rng.integers(48, 58, 1_500_000, dtype=np.uint8)), bytes(600_000)]
+
+
+def reference_record(data, garbage=None):
+    """The compiled reference (oracle/_ref) on one input: [status, bits, sha256] of `encode lzmh`, the same of
+    `decode lzmh` of that stream, and [status, bits] of `decode lzmh` of the garbage (the reference reads never-written
+    list symbols there, lzmh.c:395, :434, so only the status and the length are defined)."""
+    r = orc.ref_run_chain(data, 8 * len(data), ["encode lzmh"])
+    dr = orc.ref_run_chain(r[1], r[2], ["decode lzmh"])
+    rec = [[r[0], r[2], sha(r[1])], [dr[0], dr[2], sha(dr[1])]]
+    if garbage is not None:
+        gr = orc.ref_run_chain(garbage, 8 * len(garbage), ["decode lzmh"])
+        rec.append([gr[0], gr[2]])
+    return rec
+
+
+@pytest.fixture(scope="module")
+def recorded():
+    """The compiled reference's results on random_inputs() and long_inputs() (tests/golden/lzmh_random.json, recorded by
+    make_golden.py); where oracle/_ref is built, every record is also checked against the live reference."""
+    with open(os.path.join(GOLDEN, "lzmh_random.json")) as f:
+        return json.load(f)
+
+
+def test_lzmh_restatement_equals_compiled_reference_on_random_inputs(recorded):
+    want = recorded["random_inputs"]
+    cases = list(random_inputs())
+    assert len(want) == len(cases) == 300
+    for it, ((data, g), rec) in enumerate(zip(cases, want)):
+        if orc.have_ref():
+            assert reference_record(data, g) == rec, it
         a = orc.stage("lzmh", True, data, 8 * len(data))
-        r = orc.ref_run_chain(data, 8 * len(data), ["encode lzmh"])
-        assert a == (r[0], r[1], r[2])
+        assert [a[0], a[2], sha(a[1])] == rec[0], (it, len(data))
         d = orc.stage("lzmh", False, a[1], a[2])
-        dr = orc.ref_run_chain(a[1], a[2], ["decode lzmh"])
-        assert d == (dr[0], dr[1], dr[2]) and d[1] == data
+        assert [d[0], d[2], sha(d[1])] == rec[1], (it, len(data))
+        d = orc.stage("lzmh", False, g, 8 * len(g))
+        assert [d[0], d[2]] == rec[2], it
+
+
+def test_lzmh_restatement_equals_compiled_reference_on_long_inputs(recorded):
+    """Count saturation at 65 535 (lzmh.c:304) and back-to-back 274-byte matches: beyond what the short fixtures reach."""
+    want = recorded["long_inputs"]
+    assert len(want) == 2
+    for data, rec in zip(long_inputs(), want):
+        if orc.have_ref():
+            assert reference_record(data) == rec
+        a = orc.stage("lzmh", True, data, 8 * len(data))
+        assert [a[0], a[2], sha(a[1])] == rec[0]
+        d = orc.stage("lzmh", False, a[1], a[2])
+        assert [d[0], d[2], sha(d[1])] == rec[1] and d[1] == data

@@ -1,6 +1,6 @@
 """The oracle (oracle/dega_oracle.c, our CPU restatement) against the golden vectors generated from the compiled
-reference (tests/golden/, made by tests/golden/make_golden.py) and -- where oracle/_ref was built, i.e. in the build
-container -- against the compiled reference itself on random streams.  Bit-exact throughout."""
+reference (tests/golden/, made by tests/golden/make_golden.py) -- recorded results of the compiled reference on random
+streams among them -- and, where oracle/_ref was built, against the compiled reference itself.  Bit-exact throughout."""
 import gzip
 import hashlib
 import json
@@ -160,8 +160,8 @@ def test_error_paths():
     assert ret == 0 and np.frombuffer(b, dtype=">i4").tolist() == [0, 1]
 
 
-@pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
-def test_restatement_equals_compiled_reference_on_random_streams():
+def random_channels():
+    """The seeded random int32 channels of the comparison with the compiled reference."""
     rng = np.random.default_rng(99)
     for it in range(120):
         T = int(rng.integers(0, 500))
@@ -178,29 +178,79 @@ def test_restatement_equals_compiled_reference_on_random_streams():
             x = rng.integers(-5, 2**31, T)
         else:
             x = np.cumsum(rng.integers(-300, 301, T)) + 5000
-        x = np.asarray(x, dtype=np.int64).clip(-2**31, 2**31 - 1).astype(np.int32)
-        for ad in (0, 1):
-            got = orc.encode_i32(x, ad)
-            rr, rb, rn, _ = orc.ref_encode_i32(x, ad)
-            assert got == (rr, rb, rn), (it, ad)
-            if rr == 0:
-                assert orc.decode_i32(rb, rn, T, ad)[1].tolist() == orc.ref_decode_i32(rb, rn, T, ad)[1].tolist() == x.tolist()
-                a = orc.decode_i32(rb, 8 * len(rb), T + 8, ad)
-                b = orc.ref_decode_i32(rb, 8 * len(rb), T + 8, ad)
-                assert a[0] == b[0] and a[1].tolist() == b[1].tolist()
-    # stage level, random garbage into the decoders: same error code or same output
+        yield np.asarray(x, dtype=np.int64).clip(-2**31, 2**31 - 1).astype(np.int32)
+    # then random garbage for the decoders (the same generator, continued)
     for it in range(200):
         nbits = int(rng.integers(0, 300))
         data = rng.integers(0, 256, (nbits + 7) // 8, dtype=np.uint8).tobytes()
         if nbits % 8:
             data = data[:-1] + bytes([data[-1] & (0xFF00 >> (nbits % 8)) & 0xFF])
-        for name, spec in (("bac", "decode bac adaptive"), ("bac", "decode bac"), ("seg", "decode seg")):
-            ad = 1 if spec.endswith("adaptive") else 0
-            a = orc.stage(name, False, data, nbits, adaptive=ad)
-            r = orc.ref_run_chain(data, nbits, [spec])
-            assert a[0] == r[0], (it, spec, a[0], r[0])
-            if a[0] == 0:
-                assert (a[1], a[2]) == (r[1], r[2]), (it, spec)
+        yield data, nbits
+
+
+GARBAGE_SPECS = (("bac", "decode bac adaptive"), ("bac", "decode bac"), ("seg", "decode seg"))
+
+
+def reference_records():
+    """The compiled reference (oracle/_ref) on random_channels(): per channel and adaptive in (0, 1), [status, bits,
+    sha256] of the encoded stream and, when it encoded, [status, sha256 of the samples] of its decode with the exact bit
+    length and of its decode with the whole bytes and room for 8 more samples; per garbage stream and decoder,
+    [status, bits, sha256]."""
+    channels, garbage = [], []
+    for item in random_channels():
+        if isinstance(item, np.ndarray):
+            x, T = item, item.size
+            for ad in (0, 1):
+                rr, rb, rn, _ = orc.ref_encode_i32(x, ad)
+                rec = [[rr, rn, sha(rb)]]
+                if rr == 0:
+                    for nb, mt in ((rn, T), (8 * len(rb), T + 8)):
+                        r = orc.ref_decode_i32(rb, nb, mt, ad)
+                        rec.append([r[0], sha(r[1].tobytes())])
+                channels.append(rec)
+        else:
+            data, nbits = item
+            for _, spec in GARBAGE_SPECS:
+                r = orc.ref_run_chain(data, nbits, [spec])
+                garbage.append([r[0], r[2], sha(r[1])])
+    return {"channels": channels, "garbage": garbage}
+
+
+def test_restatement_equals_compiled_reference_on_random_streams():
+    """Against the compiled reference's results on random_channels() (tests/golden/dega_random.json, recorded by
+    make_golden.py); where oracle/_ref is built, the records are also checked against the live reference."""
+    with open(os.path.join(GOLDEN, "dega_random.json")) as f:
+        want = json.load(f)
+    if orc.have_ref():
+        assert reference_records() == want
+    channels, garbage = iter(want["channels"]), iter(want["garbage"])
+    n = 0
+    for item in random_channels():
+        if isinstance(item, np.ndarray):
+            x, T = item, item.size
+            for ad in (0, 1):
+                rec = next(channels)
+                got = orc.encode_i32(x, ad)
+                assert [got[0], got[2], sha(got[1])] == rec[0], (n, ad)
+                if got[0] == 0:
+                    d = orc.decode_i32(got[1], got[2], T, ad)
+                    assert d[1].tolist() == x.tolist() and [d[0], sha(d[1].tobytes())] == rec[1], (n, ad)
+                    d = orc.decode_i32(got[1], 8 * len(got[1]), T + 8, ad)
+                    assert [d[0], sha(d[1].tobytes())] == rec[2], (n, ad)
+                else:
+                    assert len(rec) == 1, (n, ad)
+        else:
+            # stage level, random garbage into the decoders: same error code or same output
+            data, nbits = item
+            for name, spec in GARBAGE_SPECS:
+                rec = next(garbage)
+                ad = 1 if spec.endswith("adaptive") else 0
+                a = orc.stage(name, False, data, nbits, adaptive=ad)
+                assert a[0] == rec[0], (n, spec, a[0], rec[0])
+                if a[0] == 0:
+                    assert [a[2], sha(a[1])] == rec[1:], (n, spec)
+        n += 1
+    assert n == 320 and next(channels, None) is None and next(garbage, None) is None
 
 
 def test_float_entry_at_other_value_sizes():

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r02prof
 mkdir -p $O
-B="python3 $R/bench.py --steps 3 --warmup 1 --cpu-channels 0 --no-extras --end-to-end-channels 0"
+B="python3 $R/bench.py --full --steps 3 --warmup 1 --cpu-channels 0 --no-extras --end-to-end-channels 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B > $O/stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- $B --no-round-trip > $O/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- $B --no-round-trip > $O/write.log 2>&1

@@ -25,7 +25,7 @@ quick() {  # $1 = name, rest = program: kernel stats + the instruction-mix pass 
     rocprofv3 --pmc $SQ --output-format csv -d $O/${n}_sq -- "$@" > $O/${n}_sq.log 2>&1
     rocprofv3 --pmc VALUBusy SALUBusy --output-format csv -d $O/${n}_valu -- "$@" > $O/${n}_valu.log 2>&1
 }
-COMMON="--cpu-channels 0 --no-extras --end-to-end-channels 0"
+COMMON="--full --cpu-channels 0 --no-extras --end-to-end-channels 0"
 for s in $SECTIONS; do
     case $s in
     dega) passes dega python3 $R/bench.py --steps 3 --warmup 1 $COMMON ;;
