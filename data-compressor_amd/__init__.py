@@ -83,6 +83,12 @@ _SIGNATURES = {
     "dega_hip_group_lzmh_decode": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, _P, _P]),
     "dega_hip_pinned_alloc": (_P, [_Z]),
     "dega_hip_pinned_free": (None, [_P]),
+    "dega_hip_aggregate_rows": (_Z, [_Z, _Z]),
+    "dega_hip_aggregate_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _Z, _P, _Z, _P]),
+    "dega_hip_aggregate_host": (C.c_int, [_P, _P, _Z, _Z, _Z, _Z, _P, _Z]),
+    "dega_hip_encode_agg_f32_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _Z, C.c_float, C.c_int, C.c_int, _P, _Z, _P, _P, _P]),
+    "dega_hip_encode_agg_job_host": (C.c_int, [_P, _P, _Z, _P, _P, _Z, _P, _P, _P]),
+    "dega_hip_group_encode_agg": (C.c_int, [_P, _P, _Z, _P, _P, _Z, _P, _P, _P]),
     "dega_hip_profile": (C.c_int, [_P, C.c_int]),
     "dega_hip_profile_read": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int]),
 }
@@ -144,10 +150,14 @@ class _JobCalls:
     """encode_job / decode_job on numpy arrays: the packed host-pointer surface, shared by Context (one device) and Group
     (every device).  Subclasses provide _enc_fn / _dec_fn / _handle / _check."""
 
-    def encode_job(self, x_tc, adaptive=1, valuesize=32, samples=SAMPLES_I32, factor=100.0, packed_cap=None, channels=None, packed=None):
+    def encode_job(self, x_tc, adaptive=1, valuesize=32, samples=SAMPLES_I32, factor=100.0, packed_cap=None, channels=None, packed=None, num_values=1):
         """x_tc: [T, ld] array of the sample type (channels = the first `channels` columns, default all).
-        Returns (packed uint8 [total], offsets uint64 [C+1], bits uint64 [C], err int32 [C])."""
+        Returns (packed uint8 [total], offsets uint64 [C+1], bits uint64 [C], err int32 [C]).
+        num_values != 1 (float32 samples only): every num_values consecutive readings of a channel are summed on the
+        device first, as the reference's `encode aggregate` does, and the ceil(T / num_values) sums are coded."""
         import numpy as np
+        if num_values != 1:
+            return self._encode_agg_job(x_tc, int(num_values), adaptive, valuesize, samples, factor, packed_cap, channels, packed)
         if not (isinstance(x_tc, np.ndarray) and x_tc.flags.c_contiguous and x_tc.dtype == _sample_dtype(samples)):
             x_tc = np.ascontiguousarray(x_tc, dtype=_sample_dtype(samples))
         T, pitch = x_tc.shape
@@ -166,6 +176,34 @@ class _JobCalls:
                 break
             packed_cap = int(offsets[Cn])
         self._check(ret, "encode_job")
+        return buf[: int(offsets[Cn])], offsets, bits, err
+
+    def _encode_agg_job(self, x_tc, num_values, adaptive, valuesize, samples, factor, packed_cap, channels, packed):
+        import numpy as np
+        # the layout the library is told is the layout the array has: nothing is converted or copied behind the caller's back
+        assert isinstance(x_tc, np.ndarray) and x_tc.ndim == 2 and x_tc.flags.c_contiguous, "x_tc must be a C-contiguous [T, ld] numpy array"
+        assert samples != SAMPLES_F32 or x_tc.dtype == np.float32, "float32 samples need a float32 array"
+        assert num_values >= 0
+        T, pitch = x_tc.shape
+        Cn = pitch if channels is None else int(channels)
+        assert 0 <= Cn <= pitch, "channels must be at most the row pitch"
+        assert packed is None or (isinstance(packed, np.ndarray) and packed.dtype == np.uint8 and packed.flags.c_contiguous and packed.ndim == 1)
+        job = Job(Cn, T, pitch, int(adaptive), int(valuesize), int(samples), float(factor))
+        T_out = library().dega_hip_aggregate_rows(T, num_values)
+        if packed_cap is None:
+            packed_cap = Cn * (T_out * 2 + 64)
+        offsets = np.zeros(Cn + 1, dtype=np.uint64)
+        bits = np.zeros(Cn, dtype=np.uint64)
+        err = np.zeros(Cn, dtype=np.int32)
+        ret = OK
+        for _ in range(2):
+            buf = packed if packed is not None and packed.size >= packed_cap else np.empty(max(1, packed_cap), dtype=np.uint8)
+            ret = self._enc_agg_fn()(self._handle(), C.byref(job), num_values, x_tc.ctypes.data, buf.ctypes.data, packed_cap, offsets.ctypes.data,
+                                     bits.ctypes.data, err.ctypes.data)
+            if ret != ERROR_MEMORY or int(offsets[Cn]) <= packed_cap:
+                break
+            packed_cap = int(offsets[Cn])
+        self._check(ret, "encode_job(num_values=%d)" % num_values)
         return buf[: int(offsets[Cn])], offsets, bits, err
 
     def decode_job(self, packed, offsets, bits, T, adaptive=1, valuesize=32, samples=SAMPLES_I32, factor=100.0, var=False, out=None):
@@ -243,6 +281,9 @@ class Group(_JobCalls):
     def _dec_fn(self):
         return library().dega_hip_group_decode
 
+    def _enc_agg_fn(self):
+        return library().dega_hip_group_encode_agg
+
     def _check(self, ret, what):
         if ret != OK:
             raise DegaError(ret, "%s [%s]" % (what, library().dega_hip_group_last_error(self._h).decode()))
@@ -291,6 +332,9 @@ class Context(_JobCalls):
 
     def _dec_fn(self):
         return library().dega_hip_decode_job_host
+
+    def _enc_agg_fn(self):
+        return library().dega_hip_encode_agg_job_host
 
     def __init__(self, device=0):
         self._h = _P()
@@ -377,11 +421,60 @@ class Context(_JobCalls):
         self._check(ret, "dega_hip_decode_dev")
         return x_tc, err
 
-    def encode_f32(self, v_tc, factor=100.0, adaptive=1, cap=None, valuesize=32):
-        """float32 CUDA tensor [T, C] -> streams: Normalize fused into the encode kernel (one launch)."""
+    def aggregate(self, v_tc, num_values, out=None, channels=None):
+        """float32 CUDA tensor [T, ld] -> [ceil(T / num_values), ld_out]: every num_values consecutive readings of a channel
+        summed from left to right in float32, bit for bit what the reference's `encode aggregate` writes
+        (dega_hip_aggregate_dev).  channels = the first `channels` columns (default all, as encode_job).  `out` (optional)
+        is a float32 CUDA tensor of that many rows and at least `channels` columns; columns beyond are left alone."""
+        import torch
+        assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
+        T, ld = v_tc.shape
+        Cn = ld if channels is None else int(channels)
+        assert 0 <= Cn <= ld, "channels must be at most the row pitch"
+        T_out = library().dega_hip_aggregate_rows(T, int(num_values))
+        if out is None:
+            out = torch.empty((T_out, Cn), dtype=torch.float32, device=v_tc.device)
+        assert out.dim() == 2 and out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.device == v_tc.device
+        assert out.shape[0] >= T_out and out.shape[1] >= Cn, "out must hold ceil(T / num_values) rows of at least `channels` columns"
+        ret = library().dega_hip_aggregate_dev(self._h, v_tc.data_ptr(), Cn, T, ld, int(num_values), out.data_ptr(), out.shape[1], self._stream())
+        self._check(ret, "dega_hip_aggregate_dev")
+        return out[:T_out]
+
+    def aggregate_host(self, v_tc, num_values, out=None, channels=None):
+        """The same for a float32 numpy array [T, ld] in host memory (synchronous: upload, sum, download)."""
+        import numpy as np
+        assert isinstance(v_tc, np.ndarray) and v_tc.ndim == 2 and v_tc.dtype == np.float32 and v_tc.flags.c_contiguous
+        T, ld = v_tc.shape
+        Cn = ld if channels is None else int(channels)
+        assert 0 <= Cn <= ld, "channels must be at most the row pitch"
+        T_out = library().dega_hip_aggregate_rows(T, int(num_values))
+        if out is None:
+            out = np.empty((T_out, Cn), dtype=np.float32)
+        assert isinstance(out, np.ndarray) and out.ndim == 2 and out.dtype == np.float32 and out.flags.c_contiguous
+        assert out.shape[0] >= T_out and out.shape[1] >= Cn, "out must hold ceil(T / num_values) rows of at least `channels` columns"
+        ret = library().dega_hip_aggregate_host(self._h, v_tc.ctypes.data, Cn, T, ld, int(num_values), out.ctypes.data, out.shape[1])
+        self._check(ret, "dega_hip_aggregate_host")
+        return out[:T_out]
+
+    def encode_f32(self, v_tc, factor=100.0, adaptive=1, cap=None, valuesize=32, num_values=1):
+        """float32 CUDA tensor [T, C] -> streams: Normalize fused into the encode kernel (one launch).
+        num_values != 1: the readings are summed in groups of num_values first (dega_hip_encode_agg_f32_dev: the aggregate
+        kernel, then the same encode over ceil(T / num_values) rows, on the same stream)."""
         import torch
         T, Cn = v_tc.shape
         assert v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
+        if num_values != 1:
+            num_values = int(num_values)
+            T_out = library().dega_hip_aggregate_rows(T, num_values)
+            if cap is None:
+                cap = worst_case_bytes(T_out) if valuesize <= 32 else library().dega_hip_worst_case_bytes64(T_out)
+            out = torch.zeros((Cn, cap), dtype=torch.uint8, device=v_tc.device)
+            bits = torch.zeros(Cn, dtype=torch.int64, device=v_tc.device)
+            err = torch.zeros(Cn, dtype=torch.int32, device=v_tc.device)
+            ret = library().dega_hip_encode_agg_f32_dev(self._h, v_tc.data_ptr(), Cn, T, Cn, num_values, float(factor), int(adaptive), int(valuesize),
+                                                        out.data_ptr(), cap, bits.data_ptr(), err.data_ptr(), self._stream())
+            self._check(ret, "dega_hip_encode_agg_f32_dev")
+            return out, bits, err
         if cap is None:
             cap = worst_case_bytes(T) if valuesize <= 32 else library().dega_hip_worst_case_bytes64(T)
         out = torch.zeros((Cn, cap), dtype=torch.uint8, device=v_tc.device)

@@ -10,6 +10,7 @@
 #include "../../include/dega_hip.h"
 #include "dega_kernels.hpp"
 #include "lzmh_kernels.hpp"
+#include "aggregate_kernels.hpp"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -38,6 +39,17 @@ struct dega_hip_ctx
   std::vector<hipEvent_t> ev_pool; // events handed back by profile_read, reused by the next timed launches
   int force_waves; // 0 = choose by batch size; 4 / 8 = pairs of waves per workgroup, DEGA_WAVES_PER_WORKGROUP (measurement knob)
   Pipeline *pipe;  // streams and buffers of the host-pointer entry points, created on first use
+  // The aggregated rows between the two launches of dega_hip_encode_agg_f32_dev.  The block is shared by all calls on the
+  // context, whatever their streams: agg_done is recorded behind every call's encode launch, and a call on another
+  // stream than the last one makes its stream wait for it before its aggregate launch writes the block (on the device;
+  // the host never waits).  It grows only, by doubling, and a block it has outgrown is kept until the context goes --
+  // freeing would synchronise the device; the blocks kept back sum to less than the live one.
+  float *agg_scratch;
+  size_t agg_scratch_floats;
+  std::vector<void *> agg_retired;
+  hipEvent_t agg_done;     // behind the last call's encode launch (nullptr until the first call)
+  hipStream_t agg_stream;  // the stream that call used
+  bool agg_pending;        // agg_done has been recorded
 };
 
 static int fail(dega_hip_ctx *ctx, int code, const char *what, hipError_t e)
@@ -110,6 +122,11 @@ extern "C" int dega_hip_create(int device, dega_hip_ctx **out)
   ctx->last_error[0] = '\0';
   ctx->profile = false;
   ctx->pipe = nullptr;
+  ctx->agg_scratch = nullptr;
+  ctx->agg_scratch_floats = 0;
+  ctx->agg_done = nullptr;
+  ctx->agg_stream = nullptr;
+  ctx->agg_pending = false;
   {
     const char *w = getenv("DEGA_WAVES_PER_WORKGROUP");
     const int v = w != nullptr ? atoi(w) : 0;
@@ -150,6 +167,12 @@ extern "C" void dega_hip_destroy(dega_hip_ctx *ctx)
   for (hipEvent_t e : ctx->ev_pool)
     (void)hipEventDestroy(e);
   (void)hipFree(ctx->div_magic);
+  if (ctx->agg_scratch != nullptr)
+    (void)hipFree(ctx->agg_scratch);
+  for (void *p : ctx->agg_retired)
+    (void)hipFree(p);
+  if (ctx->agg_done != nullptr)
+    (void)hipEventDestroy(ctx->agg_done);
   delete ctx;
 }
 
@@ -263,6 +286,9 @@ struct Shape
   size_t C, T, ld;
   int adaptive, valuesize, samples;
   float factor;
+  // host pipeline only: the rows on the host are agg_T fine readings per channel, summed in groups of agg_N on the device
+  // (launch_aggregate) in front of the coder; T is then the aggregated length.  agg_N = 0: no aggregation.
+  size_t agg_N = 0, agg_T = 0;
 };
 
 static int check_job_shape(dega_hip_ctx *ctx, const Shape &j, size_t cap)
@@ -550,6 +576,119 @@ extern "C" int dega_hip_denormalize_dev(dega_hip_ctx *ctx, const int32_t *x_tc, 
   hipLaunchKernelGGL(dega_denormalize_kernel, rowsplit_grid(C, T), dim3(BLOCK), 0, (hipStream_t)stream, a);
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
+}
+
+// ---- aggregate (DCLib/src/aggregate.c) --------------------------------------------------------------------------------------
+
+extern "C" size_t dega_hip_aggregate_rows(size_t T, size_t num_values)
+{
+  return num_values == 0 ? 0 : T / num_values + (T % num_values != 0 ? 1 : 0);
+}
+
+// Columns x ranges of output rows (the pattern of rowsplit_grid, cut at multiples of num_values because the unit is an
+// output row): enough workgroups for eight per CU where the batch has them, never more ranges than output rows.
+static int launch_aggregate(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t N, float *a_tc, size_t ld_out, hipStream_t s)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (N == 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: num_values must be at least 1 (the reference does not terminate on 0)", hipSuccess);
+  if (ld < C || ld_out < C)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: ld < C or ld_out < C", hipSuccess);
+  if (C == 0 || T == 0)
+    return DEGA_OK;
+  if (v_tc == nullptr || a_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0 || ((uintptr_t)a_tc & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: v_tc and a_tc must be float32 device arrays", hipSuccess);
+  const size_t T_out = dega_hip_aggregate_rows(T, N);
+  {
+    // a_tc may not alias v_tc
+    const uintptr_t v0 = (uintptr_t)v_tc, v1 = v0 + ((T - 1) * ld + C) * sizeof(float);
+    const uintptr_t a0 = (uintptr_t)a_tc, a1 = a0 + ((T_out - 1) * ld_out + C) * sizeof(float);
+    if (a0 < v1 && v0 < a1)
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: a_tc overlaps v_tc", hipSuccess);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  // four channels per lane where every row allows aligned 16-byte loads that stay inside its C values; else one
+  const bool wide = C % 4 == 0 && ld % 4 == 0 && ((uintptr_t)v_tc & 15u) == 0;
+  const size_t units = wide ? C / 4 : C;
+  const size_t gx = (units + AGG_BLOCK - 1) / AGG_BLOCK;
+  if (gx > 0x7FFFFFFFu)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: too many channels for one launch", hipSuccess);
+  size_t gy = std::min<size_t>(std::min<size_t>(T_out, 65535), std::max<size_t>(1, (2048 + gx - 1) / gx));
+  AggregateArgs a;
+  a.v = v_tc;
+  a.a = a_tc;
+  a.C = C;
+  a.T = T;
+  a.ld = ld;
+  a.N = N;
+  a.T_out = T_out;
+  a.ld_out = ld_out;
+  a.rows_per_block = (T_out + gy - 1) / gy;
+  gy = (T_out + a.rows_per_block - 1) / a.rows_per_block;
+  a.wide_out = (wide && ld_out % 4 == 0 && ((uintptr_t)a_tc & 15u) == 0) ? 1u : 0u;
+  const dim3 grid((unsigned)gx, (unsigned)gy);
+  if (wide)
+    hipLaunchKernelGGL(dega_aggregate_kernel<AggF4>, grid, dim3(AGG_BLOCK), 0, s, a);
+  else
+    hipLaunchKernelGGL(dega_aggregate_kernel<float>, grid, dim3(AGG_BLOCK), 0, s, a);
+  HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
+extern "C" int dega_hip_aggregate_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float *a_tc,
+                                      size_t ld_out, void *stream)
+{
+  return launch_aggregate(ctx, v_tc, C, T, ld, num_values, a_tc, ld_out, (hipStream_t)stream);
+}
+
+static int agg_scratch_need(dega_hip_ctx *ctx, size_t floats)
+{
+  if (floats <= ctx->agg_scratch_floats)
+    return DEGA_OK;
+  const size_t want = std::max(floats, 2 * ctx->agg_scratch_floats); // doubling: the blocks kept back sum to less than the live one
+  float *p = nullptr;
+  HIP_TRY(ctx, hipMalloc((void **)&p, want * sizeof(float)), DEGA_ERROR_MEMORY);
+  if (ctx->agg_scratch != nullptr)
+    ctx->agg_retired.push_back(ctx->agg_scratch);
+  ctx->agg_scratch = p;
+  ctx->agg_scratch_floats = want;
+  return DEGA_OK;
+}
+
+extern "C" int dega_hip_encode_agg_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float factor,
+                                           int adaptive, int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (num_values == 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: num_values must be at least 1 (the reference does not terminate on 0)", hipSuccess);
+  if (num_values == 1) // 0.0f + v differs from v for -0.0f only, and Normalize maps both zeros to 0: the same streams without the pass
+    return dega_hip_encode_f32_dev(ctx, v_tc, C, T, ld, factor, adaptive, valuesize, out, cap, out_bits, err, stream);
+  const size_t T_out = dega_hip_aggregate_rows(T, num_values);
+  const Shape j = shape_of(C, T_out, ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor);
+  int ret;
+  if ((ret = check_job_shape(ctx, j, cap)) != DEGA_OK) // everything the encode launch would refuse, before the first launch
+    return ret;
+  if (C == 0)
+    return DEGA_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = agg_scratch_need(ctx, std::max<size_t>(T_out * ld, 4))) != DEGA_OK)
+    return ret;
+  hipStream_t s = (hipStream_t)stream;
+  if (ctx->agg_done == nullptr)
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->agg_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
+  // the scratch may still be read by the encode launch of an earlier call on another stream: this stream goes on behind it
+  if (ctx->agg_pending && ctx->agg_stream != s)
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->agg_done, 0), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = launch_aggregate(ctx, v_tc, C, T, ld, num_values, ctx->agg_scratch, ld, s)) != DEGA_OK)
+    return ret;
+  ret = launch_encode(ctx, ctx->agg_scratch, j, C, out, cap, out_bits, err, s);
+  // (recorded whatever launch_encode said: the aggregate launch is on the stream and writes the scratch)
+  HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
+  ctx->agg_stream = s;
+  ctx->agg_pending = true;
+  return ret;
 }
 
 // exclusive prefix sum of ceil(bits/8) over channels: one block, chunked (C is at most a few million; not a hot path)

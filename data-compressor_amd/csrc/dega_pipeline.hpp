@@ -378,7 +378,7 @@ struct Slot
 {
   hipStream_t s = nullptr;
   GrowDev a, b, meta; // encode: a = samples, then the packed streams; b = slabs.  decode: a = packed streams, b = slabs, c = samples
-  GrowDev c;
+  GrowDev c;          // (encode with aggregation in front: c = the fine readings as uploaded, a = their sums, which the coder reads)
   GrowPin hmeta, stage;
   // few, long channels: encode uploads the rows in bands and codes every band as it lands (one launch per band, the lanes'
   // state saved in between: EncodeArgs::seg_state); decode downloads in bands beside the running kernel.  The copies'
@@ -681,15 +681,18 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, 
     return ret;
   const size_t esz = sample_bytes(j);
   const size_t cap = usual_cap(j);
-  const size_t dev_per_channel = std::max(j.T * esz + 64, cap) + 16 + cap + 64;
-  const ChunkPlan plan = plan_chunks(j.C, j.T * esz, dev_per_channel, deliver ? 0 : 1);
+  // aggregation in front of the coder (Shape::agg_N): agg_T rows cross the link, T of them are coded; a slot holds both
+  const bool agg = j.agg_N != 0;
+  const size_t rows_in = agg ? j.agg_T : j.T;
+  const size_t dev_per_channel = std::max(j.T * esz + 64, cap) + 16 + cap + 64 + (agg ? rows_in * esz + 64 : 0);
+  const ChunkPlan plan = plan_chunks(j.C, rows_in * esz, dev_per_channel, deliver ? 0 : 1);
   if (plan.nslots < 0)
     return fail(ctx, DEGA_ERROR_MEMORY, "the device's share of the batch does not fit its memory", hipSuccess);
   run.chunks.assign(plan.nchunks, EncChunk());
   run.total = 0;
   bool out_full = false;
   const bool samples_pinned = is_pinned(samples), packed_pinned = is_pinned(sink.packed);
-  const bool in_place = samples_pinned && read_in_place();
+  const bool in_place = samples_pinned && read_in_place() && !agg;
 
   TRACE("encode share: C %zu T %zu, %zu chunks of %zu channels, %d slots", j.C, j.T, plan.nchunks, plan.chunk_channels, plan.nslots);
   auto stage1 = [&](size_t k) -> int {
@@ -711,7 +714,7 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, 
     cj.C = ch.n;
     cj.ld = ch.n;
     const uint8_t *const src = (const uint8_t *)samples + ch.c0 * esz;
-    const size_t band_rows = band_rows_of(plan, j, ch.n * esz);
+    const size_t band_rows = agg ? 0 : band_rows_of(plan, j, ch.n * esz);
     ch.rows = (const uint8_t *)sl.a.p;
     ch.rows_ld = ch.n;
     void *dev_src = nullptr;
@@ -720,7 +723,19 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, 
       (void)hipGetLastError(); // (pinned, but not mapped into the device's address space: the copy engine takes it)
       dev_src = nullptr;
     }
-    if (dev_src != nullptr)
+    if (agg)
+    {
+      // Whole-chunk launches behind a copy-engine upload: the chunk's columns of all agg_T fine rows, their sums in
+      // groups of agg_N (per channel, so a chunk of channels is self-contained), then the coder over the T sums.  The
+      // link carries agg_N times what the coder sees and is the bound; no bands, no in-place read of pinned rows.
+      HIP_TRY(ctx, sl.c.need(ch.n * j.agg_T * esz + 64), DEGA_ERROR_MEMORY);
+      HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, src, j.ld * esz, ch.n * esz, j.agg_T, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
+      if ((r = launch_aggregate(ctx, (const float *)sl.c.p, ch.n, j.agg_T, ch.n, j.agg_N, (float *)sl.a.p, ch.n, sl.s)) != DEGA_OK)
+        return r;
+      if ((r = launch_encode(ctx, sl.a.p, cj, j.C, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
+        return r;
+    }
+    else if (dev_src != nullptr)
     {
       // The caller's array is pinned and the chunk is all of its columns: the kernel's filling waves fetch their rows
       // from it themselves (LDS-DMA over the link, 256-byte row segments: 8 192 x 86 400 in 65.2 ms against 66.5 ms
@@ -1274,7 +1289,7 @@ static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samp
     }
     free_b = std::min(free_b, f);
   }
-  const size_t per_channel = std::max(j.T * esz + 64, usual_cap(j)) + 16 + usual_cap(j) + 64 + 256;
+  const size_t per_channel = std::max(j.T * esz + 64, usual_cap(j)) + 16 + usual_cap(j) + 64 + 256 + (j.agg_N != 0 ? j.agg_T * esz + 64 : 0);
   size_t round_channels = std::max<size_t>(G * 512, std::min<size_t>(j.C, free_b / 10 * 6 / per_channel * G / 512 * 512));
   uint64_t base = 0;
   bool out_full = false;
@@ -1419,6 +1434,42 @@ extern "C" int dega_hip_group_encode(dega_hip_group *grp, const dega_hip_job *jo
   return encode_on_group(grp, shape_from_job(job), samples, sink);
 }
 
+// the job of the aggregated forms: float32 samples only; job->T fine readings per channel, coded as ceil(T / num_values) sums
+static int agg_job_shape(const dega_hip_job *job, size_t num_values, Shape &j)
+{
+  if (job == nullptr || num_values == 0 || job->samples != DEGA_SAMPLES_F32)
+    return DEGA_ERROR_INVALID_VALUE;
+  j = shape_from_job(job);
+  if (num_values > 1) // 1: the plain call (the same streams: Normalize maps both zeros to 0)
+  {
+    j.agg_N = num_values;
+    j.agg_T = job->T;
+    j.T = dega_hip_aggregate_rows(job->T, num_values);
+  }
+  return DEGA_OK;
+}
+
+extern "C" int dega_hip_group_encode_agg(dega_hip_group *grp, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
+                                         size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err)
+{
+  Shape j;
+  if (grp == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (agg_job_shape(job, num_values, j) != DEGA_OK || offsets == nullptr)
+  {
+    snprintf(grp->last_error, sizeof(grp->last_error), "encode_agg: num_values must be at least 1 and the job's samples DEGA_SAMPLES_F32");
+    return DEGA_ERROR_INVALID_VALUE;
+  }
+  EncodeSink sink;
+  sink.packed = packed;
+  sink.packed_cap = packed_cap;
+  sink.offsets = offsets;
+  sink.bits = out_bits;
+  sink.err = err;
+  offsets[0] = 0;
+  return encode_on_group(grp, j, samples, sink);
+}
+
 extern "C" int dega_hip_group_decode(dega_hip_group *grp, const dega_hip_job *job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits,
                                      void *samples, uint64_t *out_count, int32_t *err)
 {
@@ -1463,6 +1514,71 @@ extern "C" int dega_hip_encode_job_host(dega_hip_ctx *ctx, const dega_hip_job *j
   sink.err = err;
   offsets[0] = 0;
   return encode_on_ctx(ctx, shape_from_job(job), samples, sink);
+}
+
+extern "C" int dega_hip_encode_agg_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
+                                            size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err)
+{
+  Shape j;
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (agg_job_shape(job, num_values, j) != DEGA_OK)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode_agg: num_values must be at least 1 and the job's samples DEGA_SAMPLES_F32", hipSuccess);
+  if (offsets == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  EncodeSink sink;
+  sink.packed = packed;
+  sink.packed_cap = packed_cap;
+  sink.offsets = offsets;
+  sink.bits = out_bits;
+  sink.err = err;
+  offsets[0] = 0;
+  return encode_on_ctx(ctx, j, samples, sink);
+}
+
+// float32 rows in host memory -> their sums in host memory, synchronous: chunks of channels through the context's first
+// slot (upload, one launch, download), as many channels at a time as keep the two images under a gigabyte
+extern "C" int dega_hip_aggregate_host(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float *a_tc,
+                                       size_t ld_out)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (num_values == 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: num_values must be at least 1 (the reference does not terminate on 0)", hipSuccess);
+  if (ld < C || ld_out < C)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: ld < C or ld_out < C", hipSuccess);
+  if (C == 0 || T == 0)
+    return DEGA_OK;
+  if (v_tc == nullptr || a_tc == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  Pipeline *pl;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = pipeline_get(ctx, &pl)) != DEGA_OK)
+    return ret;
+  Slot &sl = pl->slot[0];
+  if ((ret = slot_stream(ctx, sl)) != DEGA_OK)
+    return ret;
+  const size_t T_out = dega_hip_aggregate_rows(T, num_values);
+  const size_t per_channel = (T + T_out) * sizeof(float);
+  size_t step = std::max<size_t>(1, ((size_t)1 << 30) / per_channel);
+  if (step >= 4)
+    step = step / 4 * 4; // whole 16-byte units: the chunks' images stay on the 16-byte path
+  const bool in_pinned = is_pinned(v_tc), out_pinned = is_pinned(a_tc);
+  for (size_t c0 = 0; c0 < C; c0 += step)
+  {
+    const size_t n = std::min(step, C - c0);
+    HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, sl.c.need(n * T * sizeof(float) + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.a.need(n * T_out * sizeof(float) + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, (const uint8_t *)(v_tc + c0), ld * sizeof(float), n * sizeof(float), T, in_pinned), DEGA_ERROR_LIBRARY_CALL);
+    if ((ret = launch_aggregate(ctx, (const float *)sl.c.p, n, T, n, num_values, (float *)sl.a.p, n, sl.s)) != DEGA_OK)
+      return ret;
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(a_tc + c0), ld_out * sizeof(float), sl.a.p, n * sizeof(float), T_out, out_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
 }
 
 extern "C" int dega_hip_decode_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits,

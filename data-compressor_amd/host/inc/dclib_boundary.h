@@ -145,5 +145,6 @@ enc_dec_function_t CopyBits;                         /* "copy":  plumbing / test
 enc_dec_function_t EncodeDEGA, DecodeDEGA;           /* "dega":  valuesize-bit big-endian values <-> DEGA stream (GPU) */
 enc_dec_function_t EncodeDEGAFloat, DecodeDEGAFloat; /* "fdega": raw float32 <-> DEGA stream, normalize fused (GPU) */
 enc_dec_function_t EncodeLZMHGPU, DecodeLZMHGPU;     /* "glzmh": bytes <-> the reference's LZMH stream (GPU) */
+enc_dec_function_t AggregateGPU;                     /* "gaggregate": raw float32 -> sums of num_values consecutive values (GPU); no decoder */
 
 #endif

@@ -10,6 +10,9 @@
  *            decode: the inverse (`decode bac [adaptive] # decode seg # decode diff`)
  *   "fdega"  the same with Normalize / Denormalize running inside the coder kernels: raw float32 in or out (what
  *            `decode csv` emits / `encode csv` eats), valuesize 1..64
+ *   "gaggregate"  the reference's `aggregate` on the GPU (DCLib/src/aggregate.c:9-26, table row DCLib/src/enc_dec.c:52):
+ *            raw float32 in, the sums of every num_values consecutive values out, bit for bit; encoder only, as there.
+ *            Named like "glzmh" so that it does not extend "aggregate" (prefix lookup).
  *   "glzmh"  the reference's second codec on the GPU: bytes in -> the stream `encode lzmh` produces, bit for bit, and
  *            its inverse (DCLib/src/lzmh.c:130-574).  Named so that it does not extend "lzmh" (prefix lookup).
  *
@@ -24,6 +27,8 @@
  *   dega / fdega: the input is n interleaved channels, sample-major -- i.e. the [T][C] layout the kernels want -- and the
  *                 output is a small container (all integers big-endian):
  *                   "DEGB" | u32 version = 1 | u64 C | u64 T | C x u64 bit lengths | the C streams, each padded to a whole byte
+ *   gaggregate:   the input is n interleaved channels as for fdega; the output is the same layout with
+ *                 ceil(T / num_values) values per channel (raw floats, no container)
  *   glzmh:        the input is cut into n pieces of ceil(bytes / n) bytes, each coded as a stream of its own:
  *                   "LZMB" | u32 version = 1 | u64 C | C x (u64 piece bytes, u64 bit length) | the C streams, byte padded
  */
@@ -332,6 +337,68 @@ io_int_t EncodeDEGA(bit_file_buffer_t *const in_bit_buf, bit_file_buffer_t *cons
 io_int_t EncodeDEGAFloat(bit_file_buffer_t *const in_bit_buf, bit_file_buffer_t *const out_bit_buf, const options_t *const options)
 {
   return encode_common(in_bit_buf, out_bit_buf, options, 1);
+}
+
+/* ---- aggregate on the GPU ("gaggregate") -------------------------------------------------------------------------------- */
+
+/* Aggregate (aggregate.c:9-26) over num_channels interleaved channels of raw native-endian float32 -- what `decode csv`
+   writes and "fdega" reads.  Partial input is treated as encode_common(is_float = 1) treats it.  num_values=0 makes the
+   reference loop for ever (its inner loop reads nothing, aggregate.c:16); here it is ERROR_INVALID_VALUE. */
+io_int_t AggregateGPU(bit_file_buffer_t *const in_bit_buf, bit_file_buffer_t *const out_bit_buf, const options_t *const options)
+{
+  FILE *const log = options->error_log_file;
+  const size_t C = channels_of(options);
+  const size_t N = options->num_values;
+  dega_hip_group *group;
+  dega_hip_ctx *ctx;
+  byte_vec raw = { NULL, 0, 0 };
+  uint64_t nbits = 0;
+  float *sums = NULL;
+  size_t T, T_out;
+  io_int_t ret;
+
+  if (N == 0)
+  {
+    LOG_TO(log, "gaggregate: num_values must be at least 1\n");
+    return ERROR_INVALID_VALUE;
+  }
+  if ((ret = get_group(log, &group)) != NO_ERROR)
+    return ret;
+  ctx = dega_hip_group_context(group, 0);
+  if ((ret = slurp(in_bit_buf, &raw, &nbits)) != NO_ERROR)
+    goto done;
+  if (nbits % 32 != 0) /* the reference's READ_BITS_CHECKED would stop on the short last value (aggregate.c:19) */
+  {
+    LOG_TO(log, "Only read %lu bits instead of %lu\n", (unsigned long)(nbits % 32), (unsigned long)32);
+    ret = ERROR_LIBRARY_CALL;
+    goto done;
+  }
+  if ((nbits / 32) % C != 0)
+  {
+    LOG_TO(log, "gaggregate: %lu values do not divide into %lu channels\n", (unsigned long)(nbits / 32), (unsigned long)C);
+    ret = ERROR_INVALID_VALUE;
+    goto done;
+  }
+  T = (size_t)(nbits / 32) / C;
+  T_out = dega_hip_aggregate_rows(T, N);
+  if (T_out == 0)
+    goto done; /* no input, no output (aggregate.c:11) */
+  if (mul_or_zero(mul_or_zero(T_out, C), sizeof(float)) == 0 || (sums = (float *)malloc(T_out * C * sizeof(float))) == NULL)
+  {
+    ret = ERROR_MEMORY;
+    goto done;
+  }
+  if ((ret = dega_hip_aggregate_host(ctx, (const float *)raw.p, C, T, C, N, sums, C)) != DEGA_OK)
+  {
+    LOG_TO(log, "gaggregate: %s (%s)\n", ERROR_MESSAGE_STRING(ret), dega_hip_last_error(ctx));
+    goto done;
+  }
+  if (WriteBitFileBuffer(out_bit_buf, (const uint8_t *)sums, T_out * C * 32) != (io_int_t)(T_out * C * 32))
+    ret = ERROR_LIBRARY_CALL;
+done:
+  free(raw.p);
+  free(sums);
+  return ret;
 }
 
 /* ---- decode ---------------------------------------------------------------------------------------------------------- */

@@ -1,7 +1,7 @@
 /* enc_dec.c -- plugin and option tables.  Same lookup semantics as the reference's DCLib/src/enc_dec.c:
  *   - both tables are sorted by name and searched with bsearch + a comparator that compares only strlen(table name)
  *     characters (enc_dec.c:89-98, 135-144), so a key that merely STARTS with a registered name finds it; new names
- *     therefore must not extend an existing one ("dega", "fdega" are safe; "bac_gpu" would not be);
+ *     therefore must not extend an existing one ("dega", "fdega", "gaggregate" are safe; "bac_gpu" would not be);
  *   - each codec row carries the bitmask of options it accepts (enc_dec.c:51-60);
  *   - options are stored through offsetof() into options_t by typed setters (enc_dec.c:227-283);
  *   - defaults as enc_dec.c:187-197 (valuesize 32, normalization_factor 100, adaptive off, ...).
@@ -49,6 +49,7 @@ static const codec_row_t codecs[] = { /* sorted by name */
   { "copy", "Copies input to output", { &CopyBits, &CopyBits }, OPT_BLOCKSIZE },
   { "dega", "diff + seg + bac on the GPU (MI355X), big-endian integer values in", { &EncodeDEGA, &DecodeDEGA }, OPT_ADAPTIVE | OPT_VALUESIZE | OPT_NUM_CHANNELS },
   { "fdega", "normalize + diff + seg + bac on the GPU (MI355X), raw floats in", { &EncodeDEGAFloat, &DecodeDEGAFloat }, OPT_ADAPTIVE | OPT_VALUESIZE | OPT_NORMALIZATION | OPT_NUM_CHANNELS },
+  { "gaggregate", "Sums up values on the GPU (MI355X): the floats of the reference's aggregate, bit for bit", { &AggregateGPU, NULL }, OPT_NUM_VALUES | OPT_NUM_CHANNELS }, /* No decoder, as the reference's row */
   { "glzmh", "LZMH on the GPU (MI355X): the stream of the reference's lzmh, bit for bit", { &EncodeLZMHGPU, &DecodeLZMHGPU }, OPT_NUM_CHANNELS },
 };
 static const size_t num_codecs = sizeof(codecs) / sizeof(codecs[0]);

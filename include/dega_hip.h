@@ -10,6 +10,8 @@
  *                       (DCCLI/src/cli.c:430-466) -- one call codes C independent channels instead of one.
  *   dega_hip_decode_*   DecodeBAC (bac.c:244-263) -> DecodeSEG (seg.c:82-94) -> DecodeDifferential (diff.c:25-37).
  *   dega_hip_normalize_* / dega_hip_denormalize_*   Normalize / Denormalize (DCLib/src/normalize.c:9-27, :29-41).
+ *   dega_hip_aggregate_* / dega_hip_*encode_agg*     Aggregate (DCLib/src/aggregate.c:9-26, table row DCLib/src/enc_dec.c:52;
+ *                       encoder only, as there), alone or in front of the float-entry encoder.
  *   the bit format       DCIOLib/src/bit_file_buffer.c:220-248, 297-308 (MSB-first bits, big-endian values).
  * The reference-side binding (a row in encoders_decoders[], DCLib/src/enc_dec.c:51-60, whose enc_dec_function_t
  * (DCLib/inc/enc_dec.h:11) pulls the stream out of in_bit_buf, calls these, and pushes the result into out_bit_buf)
@@ -188,6 +190,36 @@ int dega_hip_encode_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size
 int dega_hip_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld,
                             float factor, int adaptive, int valuesize, float *v_tc, uint64_t *out_count, int32_t *err, void *stream);
 
+/* ---- aggregate: coarser granularities of the same readings (DCLib/src/aggregate.c:9-26) --------------------------------- */
+/* v_tc: float32 [T][ld] -> a_tc: float32 [T_out][ld_out], T_out = dega_hip_aggregate_rows(T, num_values) = ceil(T / num_values).
+   Per channel, a_tc[j] is the sum of readings j*num_values .. min((j+1)*num_values, T) - 1 exactly as aggregate.c:13-22
+   forms it: a float32 accumulator that starts at +0.0f and takes the readings from left to right, one rounding per add --
+   bit for bit the reference's floats (a NaN is a NaN; payloads are not promised).  The last group is short when
+   num_values does not divide T (the reference stops at the end of its input, aggregate.c:21-22); num_values > T gives
+   one row, the sum of all T.  num_values = 1 is not a copy: 0.0f + v turns -0.0f into +0.0f, as in the reference.
+   Subnormal inputs and sums are kept.  A coarser level is always computed from the base series (sums of sums round
+   differently).  One lane owns a (channel, output row) pair; nothing is reassociated.
+   num_values = 0 gives DEGA_ERROR_INVALID_VALUE from every entry point below before anything is launched -- the
+   reference does not terminate on it (its inner loop reads nothing, aggregate.c:16), which is not reproduced.
+   T = 0 or C = 0: nothing is launched, DEGA_OK.  ld >= C, ld_out >= C; a_tc may not overlap v_tc.  There is no decoder,
+   as in the reference: streams coded behind an aggregation decode with dega_hip_decode_f32_* and T_out. */
+size_t dega_hip_aggregate_rows(size_t T, size_t num_values); /* ceil(T / num_values); 0 when num_values == 0 */
+int dega_hip_aggregate_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float *a_tc, size_t ld_out,
+                           void *stream);
+int dega_hip_aggregate_host(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float *a_tc, size_t ld_out);
+/* `encode aggregate num_values=N # encode normalize # encode diff # encode seg # encode bac [adaptive]` per channel: two
+   launches on `stream`, no synchronisation -- the aggregate kernel into a scratch of T_out x ld floats that the context
+   owns, then dega_hip_encode_f32_dev over the T_out sums.  Calls on one context may use different streams like those of
+   the other `dev` entry points: the scratch is shared, so a call on another stream than the previous one makes its
+   stream wait (hipStreamWaitEvent; the host does not wait) until that call's encode launch has read it -- such calls
+   run one after the other on the device.  The scratch only grows, by doubling; a block it has outgrown is never freed
+   under a kernel that may still read it: it is kept until the context is destroyed (together less than the live block).  out / cap / out_bits / err as there; cap is
+   judged against T_out (dega_hip_worst_case_bytes(T_out) always suffices), and so is the limit of 2^25 samples per
+   channel.  num_values = 1 goes straight to dega_hip_encode_f32_dev: Normalize maps both zeros to 0, the streams are
+   the same. */
+int dega_hip_encode_agg_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float factor, int adaptive,
+                                int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream);
+
 /* ---- host pointers: the pipelined path DCCLI's stage loop (DCCLI/src/cli.c:430-466) ends up on ---------------------------- */
 /* `samples` and the outputs are HOST memory (pageable or pinned).  The batch is cut into chunks of channels, each on a
    stream of its own: upload of its columns, kernels, packing, download of its stream bytes -- copies and kernels of
@@ -200,6 +232,12 @@ int dega_hip_encode_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const v
                              uint64_t *offsets, uint64_t *out_bits, int32_t *err);
 int dega_hip_decode_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits,
                              void *samples, uint64_t *out_count, int32_t *err);
+/* dega_hip_encode_job_host with the aggregation of aggregate.c in front: job->samples must be DEGA_SAMPLES_F32 (anything
+   else, and num_values = 0, give DEGA_ERROR_INVALID_VALUE), job->T is the fine-grained length; every chunk of channels
+   goes up whole, is summed, coded over ceil(T / num_values) rows and packed.  The upload is num_values times what the
+   coder sees, so the link sets the time. */
+int dega_hip_encode_agg_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
+                                 size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err);
 
 /* ---- every GPU of the node: channel ranges per device, host-side concatenate, no collective ------------------------------- */
 /* Channels are independent units (every stream starts from last_value = 0, DCLib/src/diff.c:11, and InitModel(),
@@ -220,6 +258,8 @@ int dega_hip_group_encode(dega_hip_group *group, const dega_hip_job *job, const 
                           uint64_t *offsets, uint64_t *out_bits, int32_t *err);
 int dega_hip_group_decode(dega_hip_group *group, const dega_hip_job *job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits,
                           void *samples, uint64_t *out_count, int32_t *err);
+int dega_hip_group_encode_agg(dega_hip_group *group, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
+                              size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err); /* as dega_hip_encode_agg_job_host */
 
 /* Pinned host memory for callers that can keep their samples there: copies then run at link speed without the
    runtime's staging of pageable memory.  NULL when there is no GPU runtime. */
