@@ -89,6 +89,11 @@ _SIGNATURES = {
     "dega_hip_encode_agg_f32_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _Z, C.c_float, C.c_int, C.c_int, _P, _Z, _P, _P, _P]),
     "dega_hip_encode_agg_job_host": (C.c_int, [_P, _P, _Z, _P, _P, _Z, _P, _P, _P]),
     "dega_hip_group_encode_agg": (C.c_int, [_P, _P, _Z, _P, _P, _Z, _P, _P, _P]),
+    "dega_hip_aggregate_levels_plan": (C.c_int, [_Z, _Z, _P, _Z, C.c_int, _P, _P]),
+    "dega_hip_aggregate_levels_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _Z, _P, _P, _P]),
+    "dega_hip_encode_levels_f32_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _Z, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "dega_hip_encode_levels_job_host": (C.c_int, [_P, _P, _P, _Z, _P, _P, _P, _P, _P, _P]),
+    "dega_hip_group_encode_levels": (C.c_int, [_P, _P, _P, _Z, _P, _P, _P, _P, _P, _P]),
     "dega_hip_profile": (C.c_int, [_P, C.c_int]),
     "dega_hip_profile_read": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int]),
 }
@@ -139,6 +144,28 @@ def worst_case_bytes(T):
 
 def lzmh_worst_case_bytes(n):
     return library().dega_hip_lzmh_worst_case_bytes(n)
+
+
+AGG_MAX_LEVELS = 8  # DEGA_AGG_MAX_LEVELS
+
+
+def _level_array(levels):
+    levels = [int(n) for n in levels]
+    assert all(n >= 0 for n in levels), "num_values cannot be negative"
+    return levels, (_Z * max(1, len(levels)))(*levels)
+
+
+def aggregate_levels_plan(C_, T, levels, wide=True):
+    """Which levels share a pass over the base series (dega_hip_aggregate_levels_plan; no GPU needed).
+    Returns (pass_of: list of K pass indices, step_of: list of base rows per range, one per pass)."""
+    levels, nv = _level_array(levels)
+    K = len(levels)
+    pass_of = (C.c_int * max(1, K))()
+    step_of = (_Z * max(1, K))()
+    n = library().dega_hip_aggregate_levels_plan(int(C_), int(T), nv, K, 1 if wide else 0, pass_of, step_of)
+    if n < 0:
+        raise DegaError(n, "dega_hip_aggregate_levels_plan")
+    return [int(pass_of[k]) for k in range(K)], [int(step_of[q]) for q in range(n)]
 
 
 def _sample_dtype(samples):
@@ -205,6 +232,38 @@ class _JobCalls:
             packed_cap = int(offsets[Cn])
         self._check(ret, "encode_job(num_values=%d)" % num_values)
         return buf[: int(offsets[Cn])], offsets, bits, err
+
+    def encode_job_levels(self, x_tc, levels, adaptive=1, valuesize=32, factor=100.0, packed_cap=None, channels=None):
+        """encode_job(..., samples=SAMPLES_F32, num_values=N) for every N of `levels` from ONE upload of x_tc (float32 numpy
+        [T, ld]; dega_hip_encode_levels_job_host / dega_hip_group_encode_levels).  packed_cap: None, or one size per
+        level.  Returns a list of (packed, offsets, bits, err), one per level in the order given."""
+        import numpy as np
+        assert isinstance(x_tc, np.ndarray) and x_tc.ndim == 2 and x_tc.flags.c_contiguous and x_tc.dtype == np.float32, \
+            "x_tc must be a C-contiguous float32 [T, ld] numpy array"
+        levels, nv = _level_array(levels)
+        K = len(levels)
+        T, pitch = x_tc.shape
+        Cn = pitch if channels is None else int(channels)
+        assert 0 <= Cn <= pitch, "channels must be at most the row pitch"
+        job = Job(Cn, T, pitch, int(adaptive), int(valuesize), SAMPLES_F32, float(factor))
+        rows = [library().dega_hip_aggregate_rows(T, n) for n in levels]
+        caps = [Cn * (r * 2 + 64) for r in rows] if packed_cap is None else [int(c) for c in packed_cap]
+        assert len(caps) == K, "one packed_cap per level"
+        offsets = [np.zeros(Cn + 1, dtype=np.uint64) for _ in range(K)]
+        bits = [np.zeros(Cn, dtype=np.uint64) for _ in range(K)]
+        err = [np.zeros(Cn, dtype=np.int32) for _ in range(K)]
+        ptrs = lambda arrs: (_P * max(1, K))(*[a.ctypes.data for a in arrs])  # noqa: E731
+        ret, bufs = OK, []
+        for _ in range(2):
+            bufs = [np.empty(max(1, c), dtype=np.uint8) for c in caps]
+            ret = self._enc_levels_fn()(self._handle(), C.byref(job), nv, K, x_tc.ctypes.data, ptrs(bufs), (_Z * max(1, K))(*caps), ptrs(offsets),
+                                        ptrs(bits), ptrs(err))
+            need = [int(offsets[k][Cn]) for k in range(K)]
+            if ret != ERROR_MEMORY or packed_cap is not None or all(n <= c for n, c in zip(need, caps)):
+                break
+            caps = [max(n, c) for n, c in zip(need, caps)]
+        self._check(ret, "encode_job_levels(%s)" % levels)
+        return [(bufs[k][: int(offsets[k][Cn])], offsets[k], bits[k], err[k]) for k in range(K)]
 
     def decode_job(self, packed, offsets, bits, T, adaptive=1, valuesize=32, samples=SAMPLES_I32, factor=100.0, var=False, out=None):
         """The inverse.  Returns (x [T, C] of the sample type, err) or, with var=True, (x, counts, err)."""
@@ -284,6 +343,9 @@ class Group(_JobCalls):
     def _enc_agg_fn(self):
         return library().dega_hip_group_encode_agg
 
+    def _enc_levels_fn(self):
+        return library().dega_hip_group_encode_levels
+
     def _check(self, ret, what):
         if ret != OK:
             raise DegaError(ret, "%s [%s]" % (what, library().dega_hip_group_last_error(self._h).decode()))
@@ -335,6 +397,9 @@ class Context(_JobCalls):
 
     def _enc_agg_fn(self):
         return library().dega_hip_encode_agg_job_host
+
+    def _enc_levels_fn(self):
+        return library().dega_hip_encode_levels_job_host
 
     def __init__(self, device=0):
         self._h = _P()
@@ -439,6 +504,52 @@ class Context(_JobCalls):
         ret = library().dega_hip_aggregate_dev(self._h, v_tc.data_ptr(), Cn, T, ld, int(num_values), out.data_ptr(), out.shape[1], self._stream())
         self._check(ret, "dega_hip_aggregate_dev")
         return out[:T_out]
+
+    def aggregate_levels(self, v_tc, levels, channels=None, out=None):
+        """aggregate(v_tc, N) for every N of `levels` from one pass over v_tc where the plan allows it
+        (dega_hip_aggregate_levels_dev): a list of float32 CUDA tensors [ceil(T / N), channels], in the order given, each
+        bit for bit what aggregate() gives alone.  `out` (optional): one float32 CUDA tensor per level, as in aggregate()."""
+        import torch
+        assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
+        levels, nv = _level_array(levels)
+        K = len(levels)
+        T, ld = v_tc.shape
+        Cn = ld if channels is None else int(channels)
+        assert 0 <= Cn <= ld, "channels must be at most the row pitch"
+        rows = [library().dega_hip_aggregate_rows(T, n) for n in levels]
+        if out is None:
+            out = [torch.empty((r, Cn), dtype=torch.float32, device=v_tc.device) for r in rows]
+        assert len(out) == K, "one output per level"
+        for o, r in zip(out, rows):
+            assert o.dim() == 2 and o.dtype == torch.float32 and o.is_cuda and o.is_contiguous() and o.device == v_tc.device
+            assert o.shape[0] >= r and o.shape[1] >= Cn, "every out must hold ceil(T / num_values) rows of at least `channels` columns"
+        ret = library().dega_hip_aggregate_levels_dev(self._h, v_tc.data_ptr(), Cn, T, ld, nv, K, (_P * max(1, K))(*[o.data_ptr() for o in out]),
+                                                      (_Z * max(1, K))(*[o.shape[1] for o in out]), self._stream())
+        self._check(ret, "dega_hip_aggregate_levels_dev")
+        return [o[:r] for o, r in zip(out, rows)]
+
+    def encode_f32_levels(self, v_tc, levels, factor=100.0, adaptive=1, valuesize=32, cap=None):
+        """encode_f32(v_tc, num_values=N) for every N of `levels` (dega_hip_encode_levels_f32_dev): the base series is read
+        once per pass of the plan, then one encode launch per level on the same stream.  cap: None, or one per level.
+        Returns a list of (out, bits, err), one per level in the order given."""
+        import torch
+        assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
+        levels, nv = _level_array(levels)
+        K = len(levels)
+        T, Cn = v_tc.shape
+        rows = [library().dega_hip_aggregate_rows(T, n) for n in levels]
+        if cap is None:
+            cap = [worst_case_bytes(r) if valuesize <= 32 else library().dega_hip_worst_case_bytes64(r) for r in rows]
+        cap = [int(c) for c in cap]
+        assert len(cap) == K, "one cap per level"
+        out = [torch.zeros((Cn, c), dtype=torch.uint8, device=v_tc.device) for c in cap]
+        bits = [torch.zeros(Cn, dtype=torch.int64, device=v_tc.device) for _ in range(K)]
+        err = [torch.zeros(Cn, dtype=torch.int32, device=v_tc.device) for _ in range(K)]
+        ptrs = lambda ts: (_P * max(1, K))(*[t.data_ptr() for t in ts])  # noqa: E731
+        ret = library().dega_hip_encode_levels_f32_dev(self._h, v_tc.data_ptr(), Cn, T, Cn, nv, K, float(factor), int(adaptive), int(valuesize),
+                                                       ptrs(out), (_Z * max(1, K))(*cap), ptrs(bits), ptrs(err), self._stream())
+        self._check(ret, "dega_hip_encode_levels_f32_dev")
+        return list(zip(out, bits, err))
 
     def aggregate_host(self, v_tc, num_values, out=None, channels=None):
         """The same for a float32 numpy array [T, ld] in host memory (synchronous: upload, sum, download)."""

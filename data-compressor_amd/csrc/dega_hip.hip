@@ -11,6 +11,7 @@
 #include "dega_kernels.hpp"
 #include "lzmh_kernels.hpp"
 #include "aggregate_kernels.hpp"
+#include "aggregate_levels_kernels.hpp"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,6 +21,7 @@
 #include <algorithm>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -685,6 +687,324 @@ extern "C" int dega_hip_encode_agg_f32_dev(dega_hip_ctx *ctx, const float *v_tc,
     return ret;
   ret = launch_encode(ctx, ctx->agg_scratch, j, C, out, cap, out_bits, err, s);
   // (recorded whatever launch_encode said: the aggregate launch is on the stream and writes the scratch)
+  HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
+  ctx->agg_stream = s;
+  ctx->agg_pending = true;
+  return ret;
+}
+
+// ---- several granularities from one pass over the base series (aggregate_levels_kernels.hpp) -------------------------------
+
+static_assert(DEGA_AGG_MAX_LEVELS == AGG_MAX_LEVELS, "the header's limit is the kernel's");
+
+// A pass needs this many workgroups before a level may join it.  REASONED, not measured: two workgroups per CU (256 CUs);
+// the streaming figure is about 32 KiB of loads in flight per CU, and one workgroup of the kernel holds 4 waves x 16 KiB
+// in the 16-byte form.  tools/aggbench.py --levels on a narrow batch (a few hundred channels) is the measurement that
+// would revisit it.
+constexpr size_t AGG_LEVELS_MIN_WORKGROUPS = 512;
+static size_t levels_min_workgroups() // DEGA_AGG_LEVELS_MIN_WORKGROUPS=n: measurement / test knob (1: levels share a pass whatever the batch size)
+{
+  const char *e = getenv("DEGA_AGG_LEVELS_MIN_WORKGROUPS");
+  const long long v = e != nullptr ? atoll(e) : 0;
+  return v >= 1 ? (size_t)v : AGG_LEVELS_MIN_WORKGROUPS;
+}
+
+static size_t agg_gx(size_t C, bool wide)
+{
+  const size_t units = wide ? C / 4 : C;
+  return (units + AGG_BLOCK - 1) / AGG_BLOCK;
+}
+
+static size_t gcd_of(size_t x, size_t y)
+{
+  while (y != 0)
+  {
+    const size_t r = x % y;
+    x = y;
+    y = r;
+  }
+  return x;
+}
+
+// least common multiple, anything above `top` counts as `top` (no product is formed that could wrap)
+static size_t lcm_capped(size_t x, size_t y, size_t top)
+{
+  const size_t q = y / gcd_of(x, y);
+  if (x >= top || q > top / x)
+    return top;
+  return std::min(x * q, top);
+}
+
+struct LevelsPlan
+{
+  int passes = 0;
+  int pass_of[AGG_MAX_LEVELS];
+  size_t step_of[AGG_MAX_LEVELS];
+};
+
+// 0 = fine; the levels themselves (K <= 8, no N = 0, no N twice)
+static int check_level_list(const size_t *num_values, size_t K)
+{
+  if (K > AGG_MAX_LEVELS || (K != 0 && num_values == nullptr))
+    return DEGA_ERROR_INVALID_VALUE;
+  for (size_t k = 0; k < K; k++)
+  {
+    if (num_values[k] == 0)
+      return DEGA_ERROR_INVALID_VALUE;
+    for (size_t i = 0; i < k; i++)
+      if (num_values[i] == num_values[k])
+        return DEGA_ERROR_INVALID_VALUE;
+  }
+  return DEGA_OK;
+}
+
+// Which levels share a pass.  Levels in ascending N; a level joins the first pass whose least common multiple L, with it,
+// still leaves gx x ceil(T / L) >= AGG_LEVELS_MIN_WORKGROUPS workgroups, else it opens a pass of its own.  A pass of one
+// level is launch_aggregate as it is, so the worst case is K passes: what K calls do.  There is no cap on the levels of a
+// pass: measured, eight levels in one pass take 14.1 ms where two passes of four take 16.4.
+static void plan_levels(size_t C, size_t T, const size_t *num_values, size_t K, bool wide, LevelsPlan &p)
+{
+  const size_t gx = std::max<size_t>(agg_gx(C, wide), 1), Tn = std::max<size_t>(T, 1);
+  const size_t min_workgroups = levels_min_workgroups();
+  size_t order[AGG_MAX_LEVELS], L_of[AGG_MAX_LEVELS], members[AGG_MAX_LEVELS];
+  for (size_t k = 0; k < K; k++)
+    order[k] = k;
+  std::sort(order, order + K, [&](size_t x, size_t y) { return num_values[x] < num_values[y]; });
+  p.passes = 0;
+  for (size_t i = 0; i < K; i++)
+  {
+    const size_t k = order[i], N = std::min(num_values[k], Tn);
+    int at = -1;
+    for (int q = 0; q < p.passes && at < 0 && Tn <= 0xFFFFFFFFu; q++) // (the kernel's counters are 32-bit: longer series go level by level)
+    {
+      const size_t L = lcm_capped(L_of[q], N, Tn);
+      if (gx * ((Tn + L - 1) / L) >= min_workgroups)
+      {
+        at = q;
+        L_of[q] = L;
+        members[q]++;
+      }
+    }
+    if (at < 0)
+    {
+      at = p.passes++;
+      L_of[at] = N;
+      members[at] = 1;
+    }
+    p.pass_of[k] = at;
+  }
+  const size_t want = std::max<size_t>(1, (2048 + gx - 1) / gx); // ranges launch_aggregate aims for
+  for (int q = 0; q < p.passes; q++)
+  {
+    const size_t L = L_of[q], ranges = (Tn + L - 1) / L;
+    if (members[q] == 1) // what launch_aggregate does with this level: whole output rows per range
+    {
+      const size_t gy = std::min<size_t>(std::min<size_t>(ranges, 65535), want);
+      p.step_of[q] = (ranges + gy - 1) / gy * L;
+      continue;
+    }
+    size_t m = std::max<size_t>(std::max<size_t>(1, ranges / want), (ranges + 65534) / 65535);
+    p.step_of[q] = L * m; // (L <= T < 2^32 and m <= ranges: no wrap)
+  }
+}
+
+extern "C" int dega_hip_aggregate_levels_plan(size_t C, size_t T, const size_t *num_values, size_t K, int wide, int *pass_of, size_t *step_of)
+{
+  if (check_level_list(num_values, K) != DEGA_OK || (K != 0 && (pass_of == nullptr || step_of == nullptr)))
+    return DEGA_ERROR_INVALID_VALUE;
+  LevelsPlan p;
+  plan_levels(C, T, num_values, K, wide != 0 && C % 4 == 0, p);
+  for (size_t k = 0; k < K; k++)
+    pass_of[k] = p.pass_of[k];
+  for (int q = 0; q < p.passes; q++)
+    step_of[q] = p.step_of[q];
+  return p.passes;
+}
+
+template <uint32_t K>
+static void launch_levels_pass(const float *v_tc, size_t C, size_t T, size_t ld, size_t step, bool wide, const size_t *N, float *const *a_tc,
+                               const size_t *ld_out, hipStream_t s)
+{
+  AggregateLevelsArgs<K> a;
+  a.v = v_tc;
+  a.C = C;
+  a.T = T;
+  a.ld = ld;
+  a.step = step;
+  for (uint32_t l = 0; l < K; l++)
+  {
+    a.a[l] = a_tc[l];
+    a.ld_out[l] = ld_out[l];
+    a.N[l] = (uint32_t)std::min(N[l], T);
+    a.wide_out[l] = (wide && ld_out[l] % 4 == 0 && ((uintptr_t)a_tc[l] & 15u) == 0) ? 1u : 0u;
+  }
+  const dim3 grid((unsigned)agg_gx(C, wide), (unsigned)((T + step - 1) / step));
+  if (wide)
+    hipLaunchKernelGGL((dega_aggregate_levels_kernel<AggF4, K>), grid, dim3(AGG_BLOCK), 0, s, a);
+  else
+    hipLaunchKernelGGL((dega_aggregate_levels_kernel<float, K>), grid, dim3(AGG_BLOCK), 0, s, a);
+}
+
+// Everything launch_aggregate and the pass launches would refuse, for all levels, before the first launch.
+static int check_levels_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K, float *const *a_tc,
+                            const size_t *ld_out)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (check_level_list(num_values, K) != DEGA_OK)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: at most 8 levels, every num_values at least 1, none twice", hipSuccess);
+  if (K == 0)
+    return DEGA_OK;
+  if (a_tc == nullptr || ld_out == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: a_tc and ld_out are arrays of K entries", hipSuccess);
+  if (ld < C)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: ld < C", hipSuccess);
+  for (size_t k = 0; k < K; k++)
+    if (ld_out[k] < C)
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: ld_out < C", hipSuccess);
+  if (C == 0 || T == 0)
+    return DEGA_OK;
+  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: v_tc must be a float32 device array", hipSuccess);
+  if (agg_gx(C, false) > 0x7FFFFFFFu)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: too many channels for one launch", hipSuccess);
+  uintptr_t lo[AGG_MAX_LEVELS + 1], hi[AGG_MAX_LEVELS + 1];
+  lo[K] = (uintptr_t)v_tc;
+  hi[K] = lo[K] + ((T - 1) * ld + C) * sizeof(float);
+  for (size_t k = 0; k < K; k++)
+  {
+    if (a_tc[k] == nullptr || ((uintptr_t)a_tc[k] & 3u) != 0)
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: every a_tc[k] must be a float32 device array", hipSuccess);
+    lo[k] = (uintptr_t)a_tc[k];
+    hi[k] = lo[k] + ((dega_hip_aggregate_rows(T, num_values[k]) - 1) * ld_out[k] + C) * sizeof(float);
+    if (lo[k] < hi[K] && lo[K] < hi[k])
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: an output overlaps v_tc", hipSuccess);
+    for (size_t i = 0; i < k; i++)
+      if (lo[k] < hi[i] && lo[i] < hi[k])
+        return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: two levels' outputs overlap", hipSuccess);
+  }
+  return DEGA_OK;
+}
+
+// The passes of the plan on s.  The arguments have been through check_levels_dev.
+static int launch_aggregate_levels(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
+                                   float *const *a_tc, const size_t *ld_out, hipStream_t s)
+{
+  if (K == 0 || C == 0 || T == 0)
+    return DEGA_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  const bool wide = C % 4 == 0 && ld % 4 == 0 && ((uintptr_t)v_tc & 15u) == 0; // as launch_aggregate
+  LevelsPlan p;
+  plan_levels(C, T, num_values, K, wide, p);
+  for (int q = 0; q < p.passes; q++)
+  {
+    size_t N[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS];
+    float *a[AGG_MAX_LEVELS];
+    uint32_t n = 0;
+    for (size_t k = 0; k < K; k++)
+      if (p.pass_of[k] == q)
+      {
+        N[n] = num_values[k];
+        a[n] = a_tc[k];
+        ldo[n] = ld_out[k];
+        n++;
+      }
+    if (n == 1) // the existing kernel and launcher, as they are
+    {
+      const int ret = launch_aggregate(ctx, v_tc, C, T, ld, N[0], a[0], ldo[0], s);
+      if (ret != DEGA_OK)
+        return ret;
+      continue;
+    }
+    const size_t step = p.step_of[q];
+    switch (n)
+    {
+      case 2: launch_levels_pass<2>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
+      case 3: launch_levels_pass<3>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
+      case 4: launch_levels_pass<4>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
+      case 5: launch_levels_pass<5>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
+      case 6: launch_levels_pass<6>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
+      case 7: launch_levels_pass<7>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
+      default: launch_levels_pass<8>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
+    }
+    HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+  }
+  return DEGA_OK;
+}
+
+extern "C" int dega_hip_aggregate_levels_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
+                                             float *const *a_tc, const size_t *ld_out, void *stream)
+{
+  int ret;
+  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, num_values, K, a_tc, ld_out)) != DEGA_OK)
+    return ret;
+  return launch_aggregate_levels(ctx, v_tc, C, T, ld, num_values, K, a_tc, ld_out, (hipStream_t)stream);
+}
+
+static size_t round4(size_t n)
+{
+  return (n + 3) & ~(size_t)3;
+}
+
+extern "C" int dega_hip_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
+                                              float factor, int adaptive, int valuesize, uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits,
+                                              int32_t *const *err, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (check_level_list(num_values, K) != DEGA_OK)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: at most 8 levels, every num_values at least 1, none twice", hipSuccess);
+  if (K == 0)
+    return DEGA_OK;
+  if (out == nullptr || cap == nullptr || out_bits == nullptr || err == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: out, cap, out_bits and err are arrays of K entries", hipSuccess);
+  int ret;
+  // every level's encode launch judged before the first launch (cap[k] and the 2^25 limit against level k's rows), and
+  // the levels that are summed (N = 1 is coded straight from v_tc, as dega_hip_encode_agg_f32_dev does)
+  Shape j[AGG_MAX_LEVELS];
+  size_t N[AGG_MAX_LEVELS], off[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, n = 0;
+  for (size_t k = 0; k < K; k++)
+  {
+    j[k] = shape_of(C, dega_hip_aggregate_rows(T, num_values[k]), ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor);
+    if ((ret = check_job_shape(ctx, j[k], cap[k])) != DEGA_OK)
+      return ret;
+    if (C != 0 && (out[k] == nullptr || out_bits[k] == nullptr || err[k] == nullptr))
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: null output", hipSuccess);
+    if (num_values[k] == 1)
+      continue;
+    N[n] = num_values[k];
+    off[n] = floats; // multiples of four floats: every level's sums keep the 16-byte alignment of the block
+    ldo[n] = ld;
+    floats += round4(j[k].T * ld);
+    n++;
+  }
+  if (C == 0)
+    return DEGA_OK;
+  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: v_tc must be a float32 device array", hipSuccess);
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = agg_scratch_need(ctx, std::max<size_t>(floats, 4))) != DEGA_OK)
+    return ret;
+  float *a[AGG_MAX_LEVELS];
+  for (size_t i = 0; i < n; i++)
+    a[i] = ctx->agg_scratch + off[i];
+  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, N, n, a, ldo)) != DEGA_OK)
+    return ret;
+  hipStream_t s = (hipStream_t)stream;
+  if (ctx->agg_done == nullptr)
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->agg_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
+  if (ctx->agg_pending && ctx->agg_stream != s) // the protocol of dega_hip_encode_agg_f32_dev
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->agg_done, 0), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = launch_aggregate_levels(ctx, v_tc, C, T, ld, N, n, a, ldo, s)) == DEGA_OK)
+  {
+    size_t i = 0;
+    for (size_t k = 0; k < K && ret == DEGA_OK; k++)
+    {
+      const void *rows = num_values[k] == 1 ? (const void *)v_tc : (const void *)a[i++];
+      ret = launch_encode(ctx, rows, j[k], C, out[k], cap[k], out_bits[k], err[k], s);
+    }
+  }
+  // (recorded whatever the launches said: behind the LAST encode launch that is on the stream)
   HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
   ctx->agg_stream = s;
   ctx->agg_pending = true;

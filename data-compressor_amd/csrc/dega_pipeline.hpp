@@ -928,6 +928,212 @@ static int encode_deliver(dega_hip_ctx *ctx, EncodeRun &run, uint8_t *packed, ui
   return DEGA_OK;
 }
 
+// ---- encode, several granularities from one upload (dega_hip_encode_levels_job_host) -------------------------------------------
+
+struct LevelSink // one level's outputs of one device's share
+{
+  uint8_t *packed = nullptr;
+  size_t packed_cap = 0;
+  uint64_t *offsets = nullptr; // C + 1 entries, relative to this share
+  uint64_t *bits = nullptr;
+  int32_t *err = nullptr;
+  uint64_t total = 0; // out: packed bytes of the share (the size needed when full)
+  bool full = false;  // out: packed_cap was too small; the level was sized, not delivered
+};
+
+static size_t meta_stride(size_t n) // the K MetaViews of a slot lie one behind the other, each 8-byte aligned
+{
+  return (MetaView::bytes(n) + 7) & ~(size_t)7;
+}
+
+// One device's share of a batch coded at K granularities.  A function of its own beside encode_share (whose paths stay
+// as they are), with its habits: chunks of channels on the slots' streams, nothing allocated per call beyond growing the
+// slot's buffers, only stream bytes come back, first stages two chunks ahead, a level of a chunk whose stream outgrows
+// the usual slab redone with worst-case slabs.  A chunk's fine rows cross the link ONCE; a slot holds them (c), the sums
+// of all summed levels (a), K slab regions (b) and K sets of the small arrays (meta).  When the K encode launches of a
+// chunk are done its fine rows are no longer needed, and their buffer takes the packed streams, level behind level.
+// j: C, ld, factor, adaptive, valuesize of the job; j.T the FINE length.  Always delivers (no resident phase).
+// `sized`: set once every chunk has been coded and sized, i.e. bits / err / offsets / total of every level are complete;
+// a DEGA_ERROR_MEMORY with `sized` false is a failed allocation, one with `sized` true a packed buffer that is too small.
+static int encode_levels_share(dega_hip_ctx *ctx, const Shape &j, const size_t *num_values, size_t K, const void *samples, LevelSink *sink, bool &sized)
+{
+  sized = false;
+  int ret;
+  Pipeline *pl;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = pipeline_get(ctx, &pl)) != DEGA_OK)
+    return ret;
+  const size_t esz = sizeof(float);
+  Shape lj[AGG_MAX_LEVELS]; // level k as the coder sees it
+  size_t cap[AGG_MAX_LEVELS], sum_rows = 0, cap_sum = 0;
+  for (size_t k = 0; k < K; k++)
+  {
+    lj[k] = j;
+    lj[k].T = dega_hip_aggregate_rows(j.T, num_values[k]);
+    cap[k] = usual_cap(lj[k]);
+    cap_sum += cap[k];
+    if (num_values[k] != 1) // N = 1 is coded straight from the fine rows
+      sum_rows += lj[k].T;
+    sink[k].total = 0;
+    sink[k].full = false;
+  }
+  const size_t fine_bytes = std::max(j.T * esz + 64, cap_sum); // per channel: the fine rows, later every level's packed streams
+  const size_t dev_per_channel = fine_bytes + 16 + sum_rows * esz + 16 * K + cap_sum + 64 + K * 32;
+  const ChunkPlan plan = plan_chunks(j.C, j.T * esz, dev_per_channel, 0);
+  struct LevelChunk
+  {
+    size_t c0 = 0, n = 0;
+    int slot = 0;
+    EncChunk lv[AGG_MAX_LEVELS]; // per level: rows / rows_ld / total / redone / redo_bytes
+  };
+  std::vector<LevelChunk> chunks(plan.nchunks);
+  const bool samples_pinned = is_pinned(samples);
+  bool packed_pinned[AGG_MAX_LEVELS];
+  for (size_t k = 0; k < K; k++)
+    packed_pinned[k] = is_pinned(sink[k].packed);
+  TRACE("encode levels share: C %zu T %zu, %zu levels, %zu chunks of %zu channels, %d slots", j.C, j.T, K, plan.nchunks, plan.chunk_channels, plan.nslots);
+
+  auto stage1 = [&](size_t q) -> int {
+    LevelChunk &ch = chunks[q];
+    ch.c0 = q * plan.chunk_channels;
+    ch.n = std::min(plan.chunk_channels, j.C - ch.c0);
+    ch.slot = (int)(q % (size_t)plan.nslots);
+    Slot &sl = pl->slot[ch.slot];
+    int r;
+    if ((r = slot_stream(ctx, sl)) != DEGA_OK)
+      return r;
+    const size_t n = ch.n;
+    HIP_TRY(ctx, sl.c.need(n * fine_bytes + 4096), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.a.need((sum_rows * n + 4 * K) * esz + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.b.need(n * cap_sum + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.meta.need(K * meta_stride(n)), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.hmeta.need(K * meta_stride(n)), DEGA_ERROR_MEMORY);
+    const uint8_t *const src = (const uint8_t *)samples + ch.c0 * esz;
+    HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, src, j.ld * esz, n * esz, j.T, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
+    // the sums of the summed levels: the plan's passes over the chunk's image (pitch n), every level 16-byte aligned
+    size_t N[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, m = 0;
+    float *a[AGG_MAX_LEVELS];
+    for (size_t k = 0; k < K; k++)
+    {
+      EncChunk &e = ch.lv[k];
+      e.n = n;
+      e.rows_ld = n;
+      e.redone = false;
+      e.total = 0;
+      if (num_values[k] == 1)
+      {
+        e.rows = (const uint8_t *)sl.c.p;
+        continue;
+      }
+      N[m] = num_values[k];
+      a[m] = (float *)sl.a.p + floats;
+      ldo[m] = n;
+      e.rows = (const uint8_t *)a[m];
+      floats += (lj[k].T * n + 3) & ~(size_t)3;
+      m++;
+    }
+    if ((r = check_levels_dev(ctx, (const float *)sl.c.p, n, j.T, n, N, m, a, ldo)) != DEGA_OK ||
+        (r = launch_aggregate_levels(ctx, (const float *)sl.c.p, n, j.T, n, N, m, a, ldo, sl.s)) != DEGA_OK)
+      return r;
+    size_t slab_off = 0;
+    for (size_t k = 0; k < K; k++)
+    {
+      MetaView dm((uint8_t *)sl.meta.p + k * meta_stride(n), n);
+      Shape cj = lj[k];
+      cj.C = n;
+      cj.ld = n;
+      if ((r = launch_encode(ctx, ch.lv[k].rows, cj, j.C, (uint8_t *)sl.b.p + slab_off, cap[k], dm.bits, dm.err, sl.s)) != DEGA_OK)
+        return r;
+      hipLaunchKernelGGL(dega_offsets_kernel, dim3(1), dim3(1024), 0, sl.s, dm.bits, n, dm.offsets);
+      HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+      slab_off += n * cap[k];
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(sl.hmeta.p, sl.meta.p, K * meta_stride(n), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    TRACE("levels chunk %zu stage1 enqueued", q);
+    return DEGA_OK;
+  };
+
+  auto stage2 = [&](size_t q) -> int {
+    LevelChunk &ch = chunks[q];
+    Slot &sl = pl->slot[ch.slot];
+    const size_t n = ch.n;
+    HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+    int r;
+    // first every redo (it reads the level's rows, for N = 1 the fine rows), then the gathers (which overwrite the fine rows)
+    for (size_t k = 0; k < K; k++)
+    {
+      MetaView hm((uint8_t *)sl.hmeta.p + k * meta_stride(n), n);
+      bool too_small = false;
+      if (cap[k] < worst_cap(lj[k]))
+        for (size_t i = 0; i < n && !too_small; i++)
+          too_small = hm.err[i] == DEGA_ERROR_MEMORY;
+      Shape cj = lj[k];
+      cj.C = n;
+      cj.ld = n;
+      if (too_small && (r = encode_redo_chunk(ctx, pl, sl, cj, j.C, ch.lv[k], hm)) != DEGA_OK)
+        return r;
+    }
+    size_t slab_off = 0, packed_off = 0;
+    for (size_t k = 0; k < K; k++)
+    {
+      MetaView hm((uint8_t *)sl.hmeta.p + k * meta_stride(n), n), dm((uint8_t *)sl.meta.p + k * meta_stride(n), n);
+      EncChunk &e = ch.lv[k];
+      LevelSink &out = sink[k];
+      e.total = hm.offsets[n];
+      const uint64_t base = out.total;
+      for (size_t i = 0; i < n; i++)
+      {
+        out.bits[ch.c0 + i] = hm.bits[i];
+        out.err[ch.c0 + i] = hm.err[i];
+        out.offsets[ch.c0 + i] = base + hm.offsets[i];
+      }
+      out.total += e.total;
+      const size_t slabs_at = slab_off;
+      slab_off += n * cap[k];
+      if (base + e.total > out.packed_cap)
+        out.full = true; // keep sizing: the caller learns what this level needs
+      if (out.full || e.total == 0)
+        continue;
+      if (e.redone)
+      {
+        memcpy(out.packed + base, e.redo_bytes.data(), (size_t)e.total);
+        continue;
+      }
+      const size_t packed_at = packed_off; // (not redone: at most n * cap[k] bytes, and the buffer holds n * the sum of the caps)
+      packed_off += (size_t)((e.total + 15) & ~(uint64_t)15);
+      GatherArgs g{(const uint8_t *)sl.b.p + slabs_at, cap[k], dm.offsets, n, (uint8_t *)sl.c.p + packed_at};
+      hipLaunchKernelGGL(dega_gather_kernel, dim3((unsigned)((n + WAVES - 1) / WAVES)), dim3(BLOCK), 0, sl.s, g);
+      HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+      HIP_TRY(ctx, rows_to_host(pl, sl.s, out.packed + base, (size_t)e.total, (uint8_t *)sl.c.p + packed_at, (size_t)e.total, 1, packed_pinned[k]),
+              DEGA_ERROR_LIBRARY_CALL);
+    }
+    return DEGA_OK;
+  };
+
+  const size_t ahead = std::min<size_t>((size_t)std::max(plan.nslots, 1), stages_ahead());
+  for (size_t q = 0; q < plan.nchunks + ahead; q++)
+  {
+    if (q >= ahead && q - ahead < plan.nchunks && (ret = stage2(q - ahead)) != DEGA_OK)
+      return ret;
+    if (q < plan.nchunks && (ret = stage1(q)) != DEGA_OK)
+      return ret;
+  }
+  HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
+  for (int s = 0; s < plan.nslots; s++)
+    if (pl->slot[s].s != nullptr)
+      HIP_TRY(ctx, hipStreamSynchronize(pl->slot[s].s), DEGA_ERROR_LIBRARY_CALL);
+  bool any_full = false;
+  sized = true;
+  for (size_t k = 0; k < K; k++)
+  {
+    sink[k].offsets[j.C] = sink[k].total;
+    any_full = any_full || sink[k].full;
+  }
+  if (any_full)
+    return fail(ctx, DEGA_ERROR_MEMORY, "a level's packed buffer is too small: its offsets[C] holds the size needed", hipSuccess);
+  return DEGA_OK;
+}
+
 // ---- decode ------------------------------------------------------------------------------------------------------------
 
 static int decode_share(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed, const uint64_t *offsets, const uint64_t *bits, void *samples,
@@ -1534,6 +1740,177 @@ extern "C" int dega_hip_encode_agg_job_host(dega_hip_ctx *ctx, const dega_hip_jo
   sink.err = err;
   offsets[0] = 0;
   return encode_on_ctx(ctx, j, samples, sink);
+}
+
+// ---- K granularities from one upload ---------------------------------------------------------------------------------------
+
+// the arguments of the two levels forms; `what` gets the reason of a refusal
+static int check_levels_job(const dega_hip_job *job, const size_t *num_values, size_t K, const void *samples, uint8_t *const *packed,
+                            const size_t *packed_cap, uint64_t *const *offsets, uint64_t *const *out_bits, int32_t *const *err, const char **what)
+{
+  *what = "encode levels: at most 8 levels, every num_values at least 1, none twice";
+  if (check_level_list(num_values, K) != DEGA_OK)
+    return DEGA_ERROR_INVALID_VALUE;
+  *what = "encode levels: the job's samples must be DEGA_SAMPLES_F32, ld >= C";
+  if (job == nullptr || job->samples != DEGA_SAMPLES_F32 || job->ld < job->C)
+    return DEGA_ERROR_INVALID_VALUE;
+  *what = "encode levels: packed, packed_cap, offsets, out_bits and err are arrays of K entries, samples float32 rows";
+  if (K != 0 && (packed == nullptr || packed_cap == nullptr || offsets == nullptr || out_bits == nullptr || err == nullptr))
+    return DEGA_ERROR_INVALID_VALUE;
+  for (size_t k = 0; k < K; k++)
+    if (offsets[k] == nullptr || (job->C != 0 && (out_bits[k] == nullptr || err[k] == nullptr)) || (packed[k] == nullptr && packed_cap[k] != 0))
+      return DEGA_ERROR_INVALID_VALUE;
+  if ((samples == nullptr || ((uintptr_t)samples & 3u) != 0) && job->C * job->T != 0)
+    return DEGA_ERROR_INVALID_VALUE;
+  return DEGA_OK;
+}
+
+static int encode_levels_on_group(dega_hip_group *grp, const dega_hip_job *job, const size_t *num_values, size_t K, const void *samples,
+                                  uint8_t *const *packed, const size_t *packed_cap, uint64_t *const *offsets, uint64_t *const *out_bits,
+                                  int32_t *const *err)
+{
+  if (grp == nullptr || grp->ctx.empty())
+    return DEGA_ERROR_LIBRARY_INIT;
+  const Shape j = shape_from_job(job);
+  int ret;
+  for (size_t k = 0; k < K; k++) // what the K encode launches would refuse, before anything is enqueued
+  {
+    Shape lj = j;
+    lj.T = dega_hip_aggregate_rows(j.T, num_values[k]);
+    if ((ret = check_job_shape(grp->ctx[0], lj, 0)) != DEGA_OK)
+      return group_fail(grp, ret, grp->ctx[0], 0);
+    offsets[k][0] = 0;
+  }
+  if (K == 0)
+    return DEGA_OK;
+  const size_t G = std::max<size_t>(1, std::min<size_t>(grp->ctx.size(), (j.C + 511) / 512));
+  if (G == 1)
+  {
+    LevelSink sink[AGG_MAX_LEVELS];
+    for (size_t k = 0; k < K; k++)
+    {
+      sink[k].packed = packed[k];
+      sink[k].packed_cap = packed_cap[k];
+      sink[k].offsets = offsets[k];
+      sink[k].bits = out_bits[k];
+      sink[k].err = err[k];
+    }
+    bool sized;
+    ret = encode_levels_share(grp->ctx[0], j, num_values, K, samples, sink, sized);
+    return ret == DEGA_OK ? DEGA_OK : group_fail(grp, ret, grp->ctx[0], 0);
+  }
+  // Several members: contiguous channel ranges, one host thread each; every member delivers each level into a host
+  // buffer of its own (no larger than the caller's: a share that does not fit there does not fit the call), and the
+  // caller's packed[k] is filled by host-side copies once the sizes in front are known.
+  const std::vector<size_t> cut = split_channels(j.C, G);
+  std::vector<int> rets(G, DEGA_OK), sized(G, 0);
+  std::vector<std::vector<LevelSink>> sinks(G, std::vector<LevelSink>(K));
+  std::vector<std::vector<std::unique_ptr<uint8_t[]>>> tmp(G);
+  std::vector<std::vector<std::vector<uint64_t>>> rel(G, std::vector<std::vector<uint64_t>>(K));
+  std::vector<std::thread> th;
+  for (size_t g = 0; g < G; g++)
+  {
+    tmp[g].resize(K);
+    const size_t n = cut[g + 1] - cut[g];
+    for (size_t k = 0; k < K; k++)
+    {
+      Shape lj = j;
+      lj.T = dega_hip_aggregate_rows(j.T, num_values[k]);
+      const size_t room = std::min(packed_cap[k], n * usual_cap(lj));
+      tmp[g][k].reset(new uint8_t[std::max<size_t>(room, 1)]);
+      rel[g][k].assign(n + 1, 0);
+      LevelSink &s = sinks[g][k];
+      s.packed = tmp[g][k].get();
+      s.packed_cap = room;
+      s.offsets = rel[g][k].data();
+      s.bits = out_bits[k] + cut[g];
+      s.err = err[k] + cut[g];
+    }
+    th.emplace_back([&, g, n] {
+      Shape sj = j;
+      sj.C = n;
+      const void *const src = (const uint8_t *)samples + cut[g] * sizeof(float);
+      bool ok_sized = false;
+      rets[g] = encode_levels_share(grp->ctx[g], sj, num_values, K, src, sinks[g].data(), ok_sized);
+      // A level that outgrew the member's buffer but fits the caller's (a chunk redone with worst-case slabs): once more,
+      // with what it asked for.  Decided level by level: a level that does not fit the caller's buffer either stays
+      // sized only, and the others are still delivered.
+      bool retry = false;
+      for (size_t k = 0; k < K && rets[g] == DEGA_ERROR_MEMORY && ok_sized; k++)
+        if (sinks[g][k].full && sinks[g][k].total <= packed_cap[k])
+        {
+          tmp[g][k].reset(new uint8_t[(size_t)sinks[g][k].total + 1]);
+          sinks[g][k].packed = tmp[g][k].get();
+          sinks[g][k].packed_cap = (size_t)sinks[g][k].total;
+          retry = true;
+        }
+      if (retry)
+        rets[g] = encode_levels_share(grp->ctx[g], sj, num_values, K, src, sinks[g].data(), ok_sized);
+      sized[g] = ok_sized ? 1 : 0;
+    });
+  }
+  for (std::thread &t : th)
+    t.join();
+  // any failure of a member is the call's, as in encode_on_group; DEGA_ERROR_MEMORY is "a packed buffer is too small" only
+  // where the member sized all its channels -- otherwise an allocation failed and its outputs are incomplete
+  for (size_t g = 0; g < G; g++)
+    if (rets[g] != DEGA_OK && !(rets[g] == DEGA_ERROR_MEMORY && sized[g] != 0))
+      return group_fail(grp, rets[g], grp->ctx[g], g);
+  bool any_full = false;
+  for (size_t k = 0; k < K; k++)
+  {
+    uint64_t base = 0;
+    for (size_t g = 0; g < G; g++)
+    {
+      for (size_t i = 0; i < cut[g + 1] - cut[g]; i++)
+        offsets[k][cut[g] + i] = base + rel[g][k][i];
+      base += sinks[g][k].total;
+    }
+    offsets[k][j.C] = base;
+    bool full = base > packed_cap[k];
+    for (size_t g = 0; g < G; g++)
+      full = full || sinks[g][k].full;
+    any_full = any_full || full;
+    for (size_t g = 0; g < G && !full; g++)
+      if (sinks[g][k].total > 0)
+        memcpy(packed[k] + offsets[k][cut[g]], tmp[g][k].get(), (size_t)sinks[g][k].total);
+  }
+  if (any_full)
+  {
+    snprintf(grp->last_error, sizeof(grp->last_error), "a level's packed buffer is too small: its offsets[C] holds the size needed");
+    return DEGA_ERROR_MEMORY;
+  }
+  return DEGA_OK;
+}
+
+extern "C" int dega_hip_group_encode_levels(dega_hip_group *grp, const dega_hip_job *job, const size_t *num_values, size_t K, const void *samples,
+                                            uint8_t *const *packed, const size_t *packed_cap, uint64_t *const *offsets, uint64_t *const *out_bits,
+                                            int32_t *const *err)
+{
+  if (grp == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  const char *what;
+  if (check_levels_job(job, num_values, K, samples, packed, packed_cap, offsets, out_bits, err, &what) != DEGA_OK)
+  {
+    snprintf(grp->last_error, sizeof(grp->last_error), "%s", what);
+    return DEGA_ERROR_INVALID_VALUE;
+  }
+  return encode_levels_on_group(grp, job, num_values, K, samples, packed, packed_cap, offsets, out_bits, err);
+}
+
+extern "C" int dega_hip_encode_levels_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const size_t *num_values, size_t K, const void *samples,
+                                               uint8_t *const *packed, const size_t *packed_cap, uint64_t *const *offsets, uint64_t *const *out_bits,
+                                               int32_t *const *err)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  const char *what;
+  if (check_levels_job(job, num_values, K, samples, packed, packed_cap, offsets, out_bits, err, &what) != DEGA_OK)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, what, hipSuccess);
+  dega_hip_group one;
+  one.ctx.push_back(ctx);
+  one.last_error[0] = '\0';
+  return encode_levels_on_group(&one, job, num_values, K, samples, packed, packed_cap, offsets, out_bits, err);
 }
 
 // float32 rows in host memory -> their sums in host memory, synchronous: chunks of channels through the context's first

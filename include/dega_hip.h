@@ -12,6 +12,9 @@
  *   dega_hip_normalize_* / dega_hip_denormalize_*   Normalize / Denormalize (DCLib/src/normalize.c:9-27, :29-41).
  *   dega_hip_aggregate_* / dega_hip_*encode_agg*     Aggregate (DCLib/src/aggregate.c:9-26, table row DCLib/src/enc_dec.c:52;
  *                       encoder only, as there), alone or in front of the float-entry encoder.
+ *   dega_hip_aggregate_levels_* / dega_hip_*encode_levels*   the same stage for several num_values at once, as the
+ *                       granularity study runs it: K runs of `encode aggregate num_values=N_k` over the same readings,
+ *                       the base series read (and uploaded) once.
  *   the bit format       DCIOLib/src/bit_file_buffer.c:220-248, 297-308 (MSB-first bits, big-endian values).
  * The reference-side binding (a row in encoders_decoders[], DCLib/src/enc_dec.c:51-60, whose enc_dec_function_t
  * (DCLib/inc/enc_dec.h:11) pulls the stream out of in_bit_buf, calls these, and pushes the result into out_bit_buf)
@@ -220,6 +223,37 @@ int dega_hip_aggregate_host(dega_hip_ctx *ctx, const float *v_tc, size_t C, size
 int dega_hip_encode_agg_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float factor, int adaptive,
                                 int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream);
 
+/* ---- aggregate: several granularities from one pass over the base series ------------------------------------------------- */
+/* K levels num_values[0 .. K) over the same readings, in the caller's order; outputs are arrays of K pointers / sizes in
+   that order.  Level k's result is bit for bit what dega_hip_aggregate_dev / dega_hip_encode_agg_f32_dev gives for
+   num_values[k] alone: every level is summed from the BASE series (K independent float32 accumulators per channel, each
+   takes every row; a coarser level is never formed from a finer one's sums, which round differently).  What changes is
+   the traffic: levels that share a pass are computed from one read of v_tc.
+   Which levels share a pass is decided by dega_hip_aggregate_levels_plan (no GPU needed): a pass cuts the base rows into
+   ranges of step_of[p] rows, a multiple of every N of the pass, so a level joins a pass only while the least common
+   multiple still leaves enough ranges to fill the device; else it gets a pass of its own, and a pass of one level is the
+   single-level launch.  The worst case is K passes: what K calls do.  Returns the number of passes (pass_of[k] in
+   0 .. passes - 1, step_of[p] base rows per range; for wide != 0 and C a multiple of 4 the 16-byte form's workgroup count
+   is assumed), or DEGA_ERROR_INVALID_VALUE.  The environment variable DEGA_AGG_LEVELS_MIN_WORKGROUPS=n (a measurement and
+   test knob; n = 1 lets levels share a pass whatever the batch size) replaces the workgroup floor of 512, in this
+   function and in every call that plans passes; results do not depend on it, only which kernel computes them.
+   Refused with DEGA_ERROR_INVALID_VALUE before anything is launched: K > DEGA_AGG_MAX_LEVELS, a num_values[k] of 0, the
+   same num_values twice, null or misaligned arrays, ld < C, ld_out[k] < C, an output that overlaps v_tc or another
+   level's output.  K = 0, C = 0 or T = 0: nothing is launched, DEGA_OK. */
+#define DEGA_AGG_MAX_LEVELS 8
+int dega_hip_aggregate_levels_plan(size_t C, size_t T, const size_t *num_values, size_t K, int wide, int *pass_of, size_t *step_of);
+int dega_hip_aggregate_levels_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
+                                  float *const *a_tc, const size_t *ld_out, void *stream);
+/* K x `encode aggregate num_values=N_k # encode normalize # encode diff # encode seg # encode bac [adaptive]`: the passes
+   into the context's aggregate scratch (every level's sums 16-byte aligned), then K launches of the float-entry encoder
+   on the same stream, level k over ceil(T / N_k) rows into out[k] / out_bits[k] / err[k] with cap[k] bytes per channel.
+   The scratch and its protocol are those of dega_hip_encode_agg_f32_dev (the event is recorded behind the last encode
+   launch).  A level with num_values 1 is coded straight from v_tc, as there.  cap[k] and the limit of 2^25 samples are
+   judged against level k's rows. */
+int dega_hip_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
+                                   float factor, int adaptive, int valuesize, uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits,
+                                   int32_t *const *err, void *stream);
+
 /* ---- host pointers: the pipelined path DCCLI's stage loop (DCCLI/src/cli.c:430-466) ends up on ---------------------------- */
 /* `samples` and the outputs are HOST memory (pageable or pinned).  The batch is cut into chunks of channels, each on a
    stream of its own: upload of its columns, kernels, packing, download of its stream bytes -- copies and kernels of
@@ -238,6 +272,15 @@ int dega_hip_decode_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const u
    coder sees, so the link sets the time. */
 int dega_hip_encode_agg_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
                                  size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err);
+/* dega_hip_encode_agg_job_host for K levels: job->samples must be DEGA_SAMPLES_F32, job->T is the fine length.  Every
+   chunk of channels is UPLOADED ONCE, summed by the plan's passes, then coded, sized, gathered and downloaded level by
+   level: level k's streams arrive in packed[k] (packed_cap[k] bytes) with offsets[k] (C + 1 entries), out_bits[k] and
+   err[k] exactly as K calls of dega_hip_encode_agg_job_host would deliver them.  A packed_cap[k] that is too small
+   gives DEGA_ERROR_MEMORY with the size needed in offsets[k][C]; the other levels are still delivered.  A
+   DEGA_ERROR_MEMORY whose last_error names a failed call instead is an allocation that failed: no output is valid then. */
+int dega_hip_encode_levels_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const size_t *num_values, size_t K, const void *samples,
+                                    uint8_t *const *packed, const size_t *packed_cap, uint64_t *const *offsets, uint64_t *const *out_bits,
+                                    int32_t *const *err);
 
 /* ---- every GPU of the node: channel ranges per device, host-side concatenate, no collective ------------------------------- */
 /* Channels are independent units (every stream starts from last_value = 0, DCLib/src/diff.c:11, and InitModel(),
@@ -260,6 +303,12 @@ int dega_hip_group_decode(dega_hip_group *group, const dega_hip_job *job, const 
                           void *samples, uint64_t *out_count, int32_t *err);
 int dega_hip_group_encode_agg(dega_hip_group *group, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
                               size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err); /* as dega_hip_encode_agg_job_host */
+/* as dega_hip_encode_levels_job_host.  With more than one member each of them delivers its share of each level into a
+   host buffer of its own, and packed[k] is filled by host-side copies once the sizes in front are known (coarse streams
+   are small).  More than one member on DISTINCT devices is unverified (tested with two members on one device). */
+int dega_hip_group_encode_levels(dega_hip_group *group, const dega_hip_job *job, const size_t *num_values, size_t K, const void *samples,
+                                 uint8_t *const *packed, const size_t *packed_cap, uint64_t *const *offsets, uint64_t *const *out_bits,
+                                 int32_t *const *err);
 
 /* Pinned host memory for callers that can keep their samples there: copies then run at link speed without the
    runtime's staging of pageable memory.  NULL when there is no GPU runtime. */
