@@ -94,6 +94,12 @@ _SIGNATURES = {
     "dega_hip_encode_levels_f32_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _Z, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "dega_hip_encode_levels_job_host": (C.c_int, [_P, _P, _P, _Z, _P, _P, _P, _P, _P, _P]),
     "dega_hip_group_encode_levels": (C.c_int, [_P, _P, _P, _Z, _P, _P, _P, _P, _P, _P]),
+    "dega_hip_csv_line_max": (_Z, [C.c_uint, _Z]),
+    "dega_hip_csv_worst_case_bytes": (_Z, [_Z, C.c_uint, _Z]),
+    "dega_hip_csv_write_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, C.c_uint, _Z, C.c_int, _P, _Z, _P, _P, _P]),
+    "dega_hip_csv_write_host": (C.c_int, [_P, _P, _Z, _Z, _Z, C.c_uint, _Z, C.c_int, _P, _Z, _P, _P]),
+    "dega_hip_lzmh_encode_f32_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, C.c_uint, _Z, C.c_int, _Z, _P, _Z, _P, _P, _P, _P]),
+    "dega_hip_lzmh_encode_levels_f32_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _Z, C.c_uint, _Z, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "dega_hip_profile": (C.c_int, [_P, C.c_int]),
     "dega_hip_profile_read": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int]),
 }
@@ -144,6 +150,22 @@ def worst_case_bytes(T):
 
 def lzmh_worst_case_bytes(n):
     return library().dega_hip_lzmh_worst_case_bytes(n)
+
+
+def csv_line_max(decimals=2, column=1):
+    """The longest line `encode csv` can write (dega_hip_csv_line_max; no GPU needed); 0 for options out of range."""
+    return library().dega_hip_csv_line_max(int(decimals), int(column))
+
+
+def csv_worst_case_bytes(T, decimals=2, column=1):
+    """A text stride that T readings can never overflow (dega_hip_csv_worst_case_bytes); 0 for options out of range."""
+    return library().dega_hip_csv_worst_case_bytes(int(T), int(decimals), int(column))
+
+
+def _separator(separator_char):
+    sep = ord(separator_char) if isinstance(separator_char, (str, bytes)) else int(separator_char)
+    assert 0 <= sep <= 255, "separator_char is one byte"
+    return sep
 
 
 AGG_MAX_LEVELS = 8  # DEGA_AGG_MAX_LEVELS
@@ -692,6 +714,97 @@ class Context(_JobCalls):
                                                  err.data_ptr(), self._stream())
         self._check(ret, "dega_hip_lzmh_render_dev")
         return out, lens, err
+
+    # ---- encode csv: float32 series as text, alone and in front of LZMH ------------------------------------------------
+    def csv_write(self, v_tc, decimals=2, column=1, separator_char=",", stride=None, channels=None, out=None):
+        """float32 CUDA tensor [T, ld] -> the reference's `encode csv` text per channel (dega_hip_csv_write_dev):
+        (text uint8 [channels, stride], lens int64 [channels], err int32 [channels]).  stride (a multiple of 16) defaults
+        to csv_worst_case_bytes; a channel whose text + 16 bytes does not fit it reports ERROR_MEMORY and length 0."""
+        import torch
+        assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
+        T, ld = v_tc.shape
+        Cn = ld if channels is None else int(channels)
+        assert 0 <= Cn <= ld, "channels must be at most the row pitch"
+        if stride is None:
+            stride = csv_worst_case_bytes(T, decimals, column)
+        stride = int(stride)
+        if out is None:
+            out = torch.zeros((Cn, stride), dtype=torch.uint8, device=v_tc.device)
+        assert out.dim() == 2 and out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.device == v_tc.device
+        assert out.shape[0] >= Cn and out.shape[1] == stride, "out must be [channels, stride]"
+        lens = torch.zeros(Cn, dtype=torch.int64, device=v_tc.device)
+        err = torch.zeros(Cn, dtype=torch.int32, device=v_tc.device)
+        ret = library().dega_hip_csv_write_dev(self._h, v_tc.data_ptr(), Cn, T, ld, int(decimals), int(column), _separator(separator_char),
+                                               out.data_ptr(), stride, lens.data_ptr(), err.data_ptr(), self._stream())
+        self._check(ret, "dega_hip_csv_write_dev")
+        return out[:Cn], lens, err
+
+    def csv_write_host(self, v_tc, decimals=2, column=1, separator_char=",", stride=None, channels=None):
+        """The same for a float32 numpy array [T, ld] in host memory (synchronous: upload, render, download):
+        (text uint8 [channels, stride], lens uint64 [channels], err int32 [channels])."""
+        import numpy as np
+        assert isinstance(v_tc, np.ndarray) and v_tc.ndim == 2 and v_tc.dtype == np.float32 and v_tc.flags.c_contiguous
+        T, ld = v_tc.shape
+        Cn = ld if channels is None else int(channels)
+        assert 0 <= Cn <= ld, "channels must be at most the row pitch"
+        if stride is None:
+            stride = csv_worst_case_bytes(T, decimals, column)
+        stride = int(stride)
+        out = np.zeros((Cn, stride), dtype=np.uint8)
+        lens = np.zeros(Cn, dtype=np.uint64)
+        err = np.zeros(Cn, dtype=np.int32)
+        ret = library().dega_hip_csv_write_host(self._h, v_tc.ctypes.data, Cn, T, ld, int(decimals), int(column), _separator(separator_char),
+                                                out.ctypes.data, stride, lens.ctypes.data, err.ctypes.data)
+        self._check(ret, "dega_hip_csv_write_host")
+        return out, lens, err
+
+    def lzmh_encode_f32(self, v_tc, text_stride, decimals=2, column=1, separator_char=",", cap=None, channels=None):
+        """`encode csv # encode lzmh` per channel of a float32 CUDA tensor [T, ld] (dega_hip_lzmh_encode_f32_dev): the text
+        stays in a scratch of the context, text_stride bytes per channel (a multiple of 16).
+        Returns (out uint8 [channels, cap], bits int64, text_len int64, err int32)."""
+        import torch
+        assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
+        T, ld = v_tc.shape
+        Cn = ld if channels is None else int(channels)
+        assert 0 <= Cn <= ld, "channels must be at most the row pitch"
+        text_stride = int(text_stride)
+        if cap is None:
+            cap = lzmh_worst_case_bytes(text_stride)
+        out = torch.zeros((Cn, cap), dtype=torch.uint8, device=v_tc.device)
+        bits = torch.zeros(Cn, dtype=torch.int64, device=v_tc.device)
+        text_len = torch.zeros(Cn, dtype=torch.int64, device=v_tc.device)
+        err = torch.zeros(Cn, dtype=torch.int32, device=v_tc.device)
+        ret = library().dega_hip_lzmh_encode_f32_dev(self._h, v_tc.data_ptr(), Cn, T, ld, int(decimals), int(column), _separator(separator_char),
+                                                     text_stride, out.data_ptr(), cap, bits.data_ptr(), text_len.data_ptr(), err.data_ptr(), self._stream())
+        self._check(ret, "dega_hip_lzmh_encode_f32_dev")
+        return out, bits, text_len, err
+
+    def lzmh_encode_levels_f32(self, v_tc, levels, text_stride, decimals=2, column=1, separator_char=",", cap=None, channels=None):
+        """`encode aggregate num_values=N # encode csv # encode lzmh` for every N of `levels` (dega_hip_lzmh_encode_levels_f32_dev):
+        the base series is read once per pass of the plan, then render + LZMH encode per level on the same stream.
+        text_stride: one per level (or one for all); cap: None, or one per level.
+        Returns a list of (out, bits, text_len, err), one per level in the order given."""
+        import torch
+        assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
+        levels, nv = _level_array(levels)
+        K = len(levels)
+        T, ld = v_tc.shape
+        Cn = ld if channels is None else int(channels)
+        assert 0 <= Cn <= ld, "channels must be at most the row pitch"
+        strides = [int(text_stride)] * K if isinstance(text_stride, int) else [int(s) for s in text_stride]
+        assert len(strides) == K, "one text_stride per level"
+        cap = [lzmh_worst_case_bytes(s) for s in strides] if cap is None else [int(c) for c in cap]
+        assert len(cap) == K, "one cap per level"
+        out = [torch.zeros((Cn, c), dtype=torch.uint8, device=v_tc.device) for c in cap]
+        bits = [torch.zeros(Cn, dtype=torch.int64, device=v_tc.device) for _ in range(K)]
+        text_len = [torch.zeros(Cn, dtype=torch.int64, device=v_tc.device) for _ in range(K)]
+        err = [torch.zeros(Cn, dtype=torch.int32, device=v_tc.device) for _ in range(K)]
+        ptrs = lambda ts: (_P * max(1, K))(*[t.data_ptr() for t in ts])  # noqa: E731
+        ret = library().dega_hip_lzmh_encode_levels_f32_dev(self._h, v_tc.data_ptr(), Cn, T, ld, nv, K, int(decimals), int(column),
+                                                            _separator(separator_char), (_Z * max(1, K))(*strides), ptrs(out), (_Z * max(1, K))(*cap),
+                                                            ptrs(bits), ptrs(text_len), ptrs(err), self._stream())
+        self._check(ret, "dega_hip_lzmh_encode_levels_f32_dev")
+        return list(zip(out, bits, text_len, err))
 
     def lzmh_encode_host(self, strings, cap=None):
         """strings: list of bytes objects (one per channel).  Returns (out uint8 [C, cap], bits uint64 [C], err int32 [C])."""

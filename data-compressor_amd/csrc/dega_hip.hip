@@ -12,6 +12,7 @@
 #include "lzmh_kernels.hpp"
 #include "aggregate_kernels.hpp"
 #include "aggregate_levels_kernels.hpp"
+#include "csv_kernels.hpp"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -52,6 +53,14 @@ struct dega_hip_ctx
   hipEvent_t agg_done;     // behind the last call's encode launch (nullptr until the first call)
   hipStream_t agg_stream;  // the stream that call used
   bool agg_pending;        // agg_done has been recorded
+  // The text between the launches of dega_hip_lzmh_encode_f32_dev / dega_hip_lzmh_encode_levels_f32_dev (in front of
+  // it the renderer's per-channel status and lengths): the protocol of the aggregate scratch with an event of its own,
+  // recorded behind the last launch that reads the text.  Blocks it has outgrown join agg_retired.
+  uint8_t *txt_scratch;
+  size_t txt_scratch_bytes;
+  hipEvent_t txt_done;
+  hipStream_t txt_stream;
+  bool txt_pending;
 };
 
 static int fail(dega_hip_ctx *ctx, int code, const char *what, hipError_t e)
@@ -129,6 +138,11 @@ extern "C" int dega_hip_create(int device, dega_hip_ctx **out)
   ctx->agg_done = nullptr;
   ctx->agg_stream = nullptr;
   ctx->agg_pending = false;
+  ctx->txt_scratch = nullptr;
+  ctx->txt_scratch_bytes = 0;
+  ctx->txt_done = nullptr;
+  ctx->txt_stream = nullptr;
+  ctx->txt_pending = false;
   {
     const char *w = getenv("DEGA_WAVES_PER_WORKGROUP");
     const int v = w != nullptr ? atoi(w) : 0;
@@ -175,6 +189,10 @@ extern "C" void dega_hip_destroy(dega_hip_ctx *ctx)
     (void)hipFree(p);
   if (ctx->agg_done != nullptr)
     (void)hipEventDestroy(ctx->agg_done);
+  if (ctx->txt_scratch != nullptr)
+    (void)hipFree(ctx->txt_scratch);
+  if (ctx->txt_done != nullptr)
+    (void)hipEventDestroy(ctx->txt_done);
   delete ctx;
 }
 
@@ -1186,5 +1204,375 @@ extern "C" int dega_hip_lzmh_render_dev(dega_hip_ctx *ctx, const int32_t *x_tc, 
   return DEGA_OK;
 }
 
+// ---- encode csv (DCLib/src/csv.c:46-65): float32 series as text, alone and in front of LZMH --------------------------------
+
+extern "C" size_t dega_hip_csv_line_max(unsigned decimals, size_t column)
+{
+  if (decimals > CSV_MAX_DECIMALS || column == 0)
+    return 0;
+  // '-' + the 39 digits of FLT_MAX + '.' and the decimals + '\n'
+  const size_t value = 1 + 39 + (decimals != 0 ? 1 + (size_t)decimals : 0) + 1;
+  if (column - 1 > SIZE_MAX - value)
+    return 0;
+  return column - 1 + value;
+}
+
+extern "C" size_t dega_hip_csv_worst_case_bytes(size_t T, unsigned decimals, size_t column)
+{
+  const size_t line = dega_hip_csv_line_max(decimals, column);
+  if (line == 0 || T > (SIZE_MAX - CSV_SLACK - 15) / line)
+    return 0;
+  return (T * line + CSV_SLACK + 15) & ~(size_t)15;
+}
+
+constexpr bool CSV_DEFAULT_WIDE_STORES = false; // measured at 64 Ki x 86 400: 63.7 ms with 8-byte stores, 73.6 ms with staged 64-byte blocks
+static bool csv_wide_stores() // DEGA_CSV_STORE=8 | 64: measurement / test knob, the output form of dega_csv_kernel (same bytes either way)
+{
+  const char *e = getenv("DEGA_CSV_STORE");
+  const int v = e != nullptr ? atoi(e) : 0;
+  return v == 64 ? true : (v == 8 ? false : CSV_DEFAULT_WIDE_STORES);
+}
+
+static bool ranges_overlap(const void *p, size_t np, const void *q, size_t nq)
+{
+  const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+  return np != 0 && nq != 0 && p0 < q0 + nq && q0 < p0 + np;
+}
+
+// The options of the stage and the text layout (everything but the pointers), for every entry point that renders.
+static int check_csv_options(dega_hip_ctx *ctx, size_t C, size_t ld, unsigned decimals, size_t column, int separator_char, size_t stride)
+{
+  if (decimals > CSV_MAX_DECIMALS || column == 0 || separator_char < 0 || separator_char > 255)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: num_decimal_places 0..6, column at least 1, separator_char one byte", hipSuccess);
+  if (stride < 16 || (stride & 15u) != 0 || stride > 0x7FFFFFF0u || column - 1 >= stride)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: stride must be a multiple of 16 (16 .. 0x7FFFFFF0) and longer than the empty columns", hipSuccess);
+  if (ld < C)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: ld < C", hipSuccess);
+  return DEGA_OK;
+}
+
+// The arguments have been checked; C and T are not 0.
+static int launch_csv(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column, int separator_char,
+                      uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, hipStream_t s)
+{
+  const size_t gx = (C + CSV_BLOCK - 1) / CSV_BLOCK;
+  if (gx > 0x7FFFFFFFu)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: too many channels for one launch", hipSuccess);
+  CsvArgs a;
+  a.v = v_tc;
+  a.C = C;
+  a.T = T;
+  a.ld = ld;
+  a.decimals = decimals;
+  a.nsep = (uint32_t)(column - 1);
+  a.sep = (uint32_t)separator_char;
+  a.out = out;
+  a.stride = stride;
+  a.out_len = out_len;
+  a.err = err;
+  if (csv_wide_stores())
+    hipLaunchKernelGGL(dega_csv_kernel<CsvStore64>, dim3((unsigned)gx), dim3(CSV_BLOCK), 0, s, a);
+  else
+    hipLaunchKernelGGL(dega_csv_kernel<CsvStore8>, dim3((unsigned)gx), dim3(CSV_BLOCK), 0, s, a);
+  HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
+extern "C" int dega_hip_csv_write_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column,
+                                      int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, stride)) != DEGA_OK)
+    return ret;
+  if (!aligned16(out))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out must be 16-byte aligned", hipSuccess);
+  if (C == 0)
+    return DEGA_OK;
+  if (out == nullptr || out_len == nullptr || err == nullptr || ((uintptr_t)out_len & 7u) != 0 || ((uintptr_t)err & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out, out_len and err must be device arrays", hipSuccess);
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  hipStream_t s = (hipStream_t)stream;
+  if (T == 0) // no reading, no text: lengths 0, nothing launched
+  {
+    HIP_TRY(ctx, hipMemsetAsync(out_len, 0, C * sizeof(uint64_t), s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipMemsetAsync(err, 0, C * sizeof(int32_t), s), DEGA_ERROR_LIBRARY_CALL);
+    return DEGA_OK;
+  }
+  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: v_tc must be a float32 device array", hipSuccess);
+  if (ranges_overlap(out, C * stride, v_tc, ((T - 1) * ld + C) * sizeof(float)))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out overlaps v_tc", hipSuccess);
+  return launch_csv(ctx, v_tc, C, T, ld, decimals, column, separator_char, out, stride, out_len, err, s);
+}
+
+// A channel whose text did not fit its row was coded as the empty text: it reports the renderer's status and no stream.
+__global__ void __launch_bounds__(256) dega_csv_status_kernel(const int32_t *csv_err, size_t C, int32_t *err, uint64_t *out_bits)
+{
+  const size_t c = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (c < C && csv_err[c] != 0)
+  {
+    err[c] = csv_err[c];
+    out_bits[c] = 0;
+  }
+}
+
+static size_t round16(size_t n)
+{
+  return (n + 15) & ~(size_t)15;
+}
+
+// The text scratch: [C] int32 renderer status | [C] uint64 text lengths | [C][text_stride] text, each 16-byte aligned.
+struct TextScratch
+{
+  int32_t *csv_err;
+  uint64_t *len;
+  uint8_t *text;
+};
+
+static int txt_scratch_need(dega_hip_ctx *ctx, size_t C, size_t text_stride, TextScratch &t)
+{
+  const size_t head = round16(C * sizeof(int32_t)) + round16(C * sizeof(uint64_t));
+  if (C > (SIZE_MAX - head) / text_stride)
+    return fail(ctx, DEGA_ERROR_MEMORY, "csv: the text of the batch does not fit the address space", hipSuccess);
+  const size_t bytes = head + C * text_stride;
+  if (bytes > ctx->txt_scratch_bytes)
+  {
+    const size_t want = std::max(bytes, 2 * ctx->txt_scratch_bytes); // grow-only, by doubling: the protocol of agg_scratch_need
+    uint8_t *p = nullptr;
+    HIP_TRY(ctx, hipMalloc((void **)&p, want), DEGA_ERROR_MEMORY);
+    if (ctx->txt_scratch != nullptr)
+      ctx->agg_retired.push_back(ctx->txt_scratch); // (a kernel may still read it: kept until the context goes)
+    ctx->txt_scratch = p;
+    ctx->txt_scratch_bytes = want;
+  }
+  t.csv_err = (int32_t *)ctx->txt_scratch;
+  t.len = (uint64_t *)(ctx->txt_scratch + round16(C * sizeof(int32_t)));
+  t.text = ctx->txt_scratch + head;
+  return DEGA_OK;
+}
+
+// what dega_hip_lzmh_encode_dev would refuse, and the arrays of one level
+static int check_lzmh_outputs(dega_hip_ctx *ctx, size_t C, const uint8_t *out, size_t cap, const uint64_t *out_bits, const int32_t *err)
+{
+  if ((cap & 15u) != 0 || cap < 48 || !aligned16(out))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode: cap must be a multiple of 16 (>= 48), out 16-byte aligned", hipSuccess);
+  if (C != 0 && (out == nullptr || out_bits == nullptr || err == nullptr))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode: null output", hipSuccess);
+  return DEGA_OK;
+}
+
+// render + LZMH encode + status on s; the text scratch is the caller's to guard (event protocol)
+static int launch_csv_lzmh(dega_hip_ctx *ctx, const float *rows, size_t C, size_t T, size_t ld, unsigned decimals, size_t column, int separator_char,
+                           const TextScratch &t, size_t text_stride, uint8_t *out, size_t cap, uint64_t *out_bits, uint64_t *text_len, int32_t *err,
+                           hipStream_t s, bool *rendered, hipEvent_t rows_read)
+{
+  uint64_t *const len = text_len != nullptr ? text_len : t.len;
+  int ret;
+  if ((ret = launch_csv(ctx, rows, C, T, ld, decimals, column, separator_char, t.text, text_stride, len, t.csv_err, s)) != DEGA_OK)
+    return ret;
+  *rendered = true;
+  if (rows_read != nullptr) // the caller's event for "`rows` may be overwritten"
+    HIP_TRY(ctx, hipEventRecord(rows_read, s), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = dega_hip_lzmh_encode_dev(ctx, t.text, text_stride, len, C, out, cap, out_bits, err, s)) != DEGA_OK)
+    return ret;
+  hipLaunchKernelGGL(dega_csv_status_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, t.csv_err, C, err, out_bits);
+  HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
+static int zero_lzmh_outputs(dega_hip_ctx *ctx, size_t C, uint64_t *out_bits, uint64_t *text_len, int32_t *err, hipStream_t s)
+{
+  HIP_TRY(ctx, hipMemsetAsync(out_bits, 0, C * sizeof(uint64_t), s), DEGA_ERROR_LIBRARY_CALL);
+  HIP_TRY(ctx, hipMemsetAsync(err, 0, C * sizeof(int32_t), s), DEGA_ERROR_LIBRARY_CALL);
+  if (text_len != nullptr)
+    HIP_TRY(ctx, hipMemsetAsync(text_len, 0, C * sizeof(uint64_t), s), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
+extern "C" int dega_hip_lzmh_encode_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column,
+                                            int separator_char, size_t text_stride, uint8_t *out, size_t cap, uint64_t *out_bits, uint64_t *text_len,
+                                            int32_t *err, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, text_stride)) != DEGA_OK)
+    return ret;
+  if ((ret = check_lzmh_outputs(ctx, C, out, cap, out_bits, err)) != DEGA_OK)
+    return ret;
+  if (C == 0)
+    return DEGA_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  hipStream_t s = (hipStream_t)stream;
+  if (T == 0)
+    return zero_lzmh_outputs(ctx, C, out_bits, text_len, err, s);
+  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: v_tc must be a float32 device array", hipSuccess);
+  if (ranges_overlap(out, C * cap, v_tc, ((T - 1) * ld + C) * sizeof(float)))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode: out overlaps v_tc", hipSuccess);
+  TextScratch t;
+  if ((ret = txt_scratch_need(ctx, C, text_stride, t)) != DEGA_OK)
+    return ret;
+  if (ctx->txt_done == nullptr)
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txt_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
+  // the text may still be read by the LZMH launch of an earlier call on another stream: this stream goes on behind it
+  if (ctx->txt_pending && ctx->txt_stream != s)
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->txt_done, 0), DEGA_ERROR_LIBRARY_CALL);
+  bool rendered = false;
+  ret = launch_csv_lzmh(ctx, v_tc, C, T, ld, decimals, column, separator_char, t, text_stride, out, cap, out_bits, text_len, err, s, &rendered, nullptr);
+  if (rendered) // (whatever the later launches said: the renderer is on the stream and writes the scratch)
+  {
+    HIP_TRY(ctx, hipEventRecord(ctx->txt_done, s), DEGA_ERROR_LIBRARY_CALL);
+    ctx->txt_stream = s;
+    ctx->txt_pending = true;
+  }
+  return ret;
+}
+
+extern "C" int dega_hip_lzmh_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
+                                                   unsigned decimals, size_t column, int separator_char, const size_t *text_stride, uint8_t *const *out,
+                                                   const size_t *cap, uint64_t *const *out_bits, uint64_t *const *text_len, int32_t *const *err,
+                                                   void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (check_level_list(num_values, K) != DEGA_OK)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: at most 8 levels, every num_values at least 1, none twice", hipSuccess);
+  if (K == 0)
+    return DEGA_OK;
+  if (text_stride == nullptr || out == nullptr || cap == nullptr || out_bits == nullptr || err == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: text_stride, out, cap, out_bits and err are arrays of K entries", hipSuccess);
+  int ret;
+  size_t rows[AGG_MAX_LEVELS], off[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, widest = 0;
+  for (size_t k = 0; k < K; k++) // every level judged before the first launch
+  {
+    if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, text_stride[k])) != DEGA_OK)
+      return ret;
+    if ((ret = check_lzmh_outputs(ctx, C, out[k], cap[k], out_bits[k], err[k])) != DEGA_OK)
+      return ret;
+    for (size_t i = 0; i < k; i++)
+      if (ranges_overlap(out[k], C * cap[k], out[i], C * cap[i]))
+        return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: two levels' outputs overlap", hipSuccess);
+    rows[k] = dega_hip_aggregate_rows(T, num_values[k]);
+    off[k] = floats; // multiples of four floats, as dega_hip_encode_levels_f32_dev lays them out
+    ldo[k] = ld;
+    floats += round4(rows[k] * ld);
+    widest = std::max(widest, text_stride[k]);
+  }
+  if (C == 0)
+    return DEGA_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  hipStream_t s = (hipStream_t)stream;
+  if (T == 0)
+  {
+    for (size_t k = 0; k < K; k++)
+      if ((ret = zero_lzmh_outputs(ctx, C, out_bits[k], text_len != nullptr ? text_len[k] : nullptr, err[k], s)) != DEGA_OK)
+        return ret;
+    return DEGA_OK;
+  }
+  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: v_tc must be a float32 device array", hipSuccess);
+  for (size_t k = 0; k < K; k++)
+    if (ranges_overlap(out[k], C * cap[k], v_tc, ((T - 1) * ld + C) * sizeof(float)))
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: an output overlaps v_tc", hipSuccess);
+  if ((ret = agg_scratch_need(ctx, std::max<size_t>(floats, 4))) != DEGA_OK)
+    return ret;
+  float *a[AGG_MAX_LEVELS];
+  for (size_t k = 0; k < K; k++)
+    a[k] = ctx->agg_scratch + off[k];
+  // every level through the aggregate stage, num_values 1 included: the chain has `aggregate` in it (+0.0f + v)
+  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, num_values, K, a, ldo)) != DEGA_OK)
+    return ret;
+  TextScratch t;
+  if ((ret = txt_scratch_need(ctx, C, widest, t)) != DEGA_OK) // the largest level's text; reused level after level in stream order
+    return ret;
+  if (ctx->agg_done == nullptr)
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->agg_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
+  if (ctx->txt_done == nullptr)
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txt_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
+  if (ctx->agg_pending && ctx->agg_stream != s)
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->agg_done, 0), DEGA_ERROR_LIBRARY_CALL);
+  if (ctx->txt_pending && ctx->txt_stream != s)
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->txt_done, 0), DEGA_ERROR_LIBRARY_CALL);
+  bool rendered = false;
+  ret = launch_aggregate_levels(ctx, v_tc, C, T, ld, num_values, K, a, ldo, s);
+  for (size_t k = 0; k < K && ret == DEGA_OK; k++)
+  {
+    ret = launch_csv_lzmh(ctx, a[k], C, rows[k], ld, decimals, column, separator_char, t, text_stride[k], out[k], cap[k], out_bits[k],
+                          text_len != nullptr ? text_len[k] : nullptr, err[k], s, &rendered, k + 1 == K ? ctx->agg_done : nullptr);
+  }
+  // (recorded whatever the launches said.  When all went well the sums' event is already on the stream, behind the last
+  // renderer -- their last reader; what follows it only reads the text)
+  if (ret != DEGA_OK)
+    HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
+  ctx->agg_stream = s;
+  ctx->agg_pending = true;
+  if (rendered)
+  {
+    HIP_TRY(ctx, hipEventRecord(ctx->txt_done, s), DEGA_ERROR_LIBRARY_CALL);
+    ctx->txt_stream = s;
+    ctx->txt_pending = true;
+  }
+  return ret;
+}
+
 // ---- host-pointer entry points: the pipeline and the multi-device group ------------------------------------------------------
 #include "dega_pipeline.hpp"
+
+// float32 rows in host memory -> their text in host memory, synchronous, in the manner of dega_hip_aggregate_host: chunks of
+// channels through the context's first slot (upload, one launch, download), as many channels at a time as keep the
+// readings and their text under a gigabyte
+extern "C" int dega_hip_csv_write_host(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column,
+                                       int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, stride)) != DEGA_OK)
+    return ret;
+  if (C == 0)
+    return DEGA_OK;
+  if (out == nullptr || out_len == nullptr || err == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out, out_len and err must be arrays", hipSuccess);
+  if (T == 0)
+  {
+    memset(out_len, 0, C * sizeof(uint64_t));
+    memset(err, 0, C * sizeof(int32_t));
+    return DEGA_OK;
+  }
+  if (v_tc == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: v_tc must be a float32 array", hipSuccess);
+  Pipeline *pl;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = pipeline_get(ctx, &pl)) != DEGA_OK)
+    return ret;
+  Slot &sl = pl->slot[0];
+  if ((ret = slot_stream(ctx, sl)) != DEGA_OK)
+    return ret;
+  const size_t per_channel = T * sizeof(float) + stride;
+  size_t step = std::max<size_t>(1, ((size_t)1 << 30) / per_channel);
+  if (step >= 4)
+    step = step / 4 * 4;
+  const bool in_pinned = is_pinned(v_tc), out_pinned = is_pinned(out), len_pinned = is_pinned(out_len), err_pinned = is_pinned(err);
+  for (size_t c0 = 0; c0 < C; c0 += step)
+  {
+    const size_t n = std::min(step, C - c0);
+    HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, sl.c.need(n * T * sizeof(float) + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.a.need(n * stride + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.meta.need(n * (sizeof(uint64_t) + sizeof(int32_t)) + 64), DEGA_ERROR_MEMORY);
+    uint64_t *const d_len = (uint64_t *)sl.meta.p;
+    int32_t *const d_err = (int32_t *)((uint8_t *)sl.meta.p + n * sizeof(uint64_t));
+    HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, (const uint8_t *)(v_tc + c0), ld * sizeof(float), n * sizeof(float), T, in_pinned), DEGA_ERROR_LIBRARY_CALL);
+    if ((ret = launch_csv(ctx, (const float *)sl.c.p, n, T, n, decimals, column, separator_char, (uint8_t *)sl.a.p, stride, d_len, d_err, sl.s)) != DEGA_OK)
+      return ret;
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, out + c0 * stride, stride, sl.a.p, stride, n, out_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(out_len + c0), n * sizeof(uint64_t), d_len, n * sizeof(uint64_t), 1, len_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(err + c0), n * sizeof(int32_t), d_err, n * sizeof(int32_t), 1, err_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}

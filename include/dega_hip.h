@@ -15,6 +15,9 @@
  *   dega_hip_aggregate_levels_* / dega_hip_*encode_levels*   the same stage for several num_values at once, as the
  *                       granularity study runs it: K runs of `encode aggregate num_values=N_k` over the same readings,
  *                       the base series read (and uploaded) once.
+ *   dega_hip_csv_* / dega_hip_lzmh_encode*_f32_*     WriteCSV (DCLib/src/csv.c:46-65, table row DCLib/src/enc_dec.c:55; the
+ *                       writer only -- ReadCSV is not replaced), alone or between `aggregate` and LZMH: the chain
+ *                       `encode aggregate # encode csv # encode lzmh` of the granularity study's second codec.
  *   the bit format       DCIOLib/src/bit_file_buffer.c:220-248, 297-308 (MSB-first bits, big-endian values).
  * The reference-side binding (a row in encoders_decoders[], DCLib/src/enc_dec.c:51-60, whose enc_dec_function_t
  * (DCLib/inc/enc_dec.h:11) pulls the stream out of in_bit_buf, calls these, and pushes the result into out_bit_buf)
@@ -253,6 +256,62 @@ int dega_hip_aggregate_levels_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C
 int dega_hip_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
                                    float factor, int adaptive, int valuesize, uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits,
                                    int32_t *const *err, void *stream);
+
+/* ---- encode csv: a float32 series as text (WriteCSV, DCLib/src/csv.c:46-65) ------------------------------------------------ */
+/* v_tc: float32 [T][ld] -> out: uint8 [C][stride], channel c's text at out + c * stride, out_len[c] bytes of it: for every
+   reading `column - 1` copies of separator_char (csv.c:56-59), then what sprintf("%.*f\n", num_decimal_places, value)
+   writes (csv.c:60), byte for byte as glibc prints it: a '-' exactly when the sign BIT is set (-0.0f gives -0.00, a NaN
+   with the bit set -nan), inf / nan without decimals, else the exact value of the float rounded half-to-even to
+   `decimals` = num_decimal_places = 0 .. 6 (DCLib/src/enc_dec.c:69) places, every integer digit printed (FLT_MAX has 39),
+   no decimal point at 0 decimals, subnormals included.  Integer arithmetic only.  One limit of the reference is NOT
+   reproduced: its line buffer has 48 bytes (csv.c:11), so it overruns on lines of 48 characters and more (negative values
+   of magnitude 1e38 and above at 6 decimals); the device writes what printf would write.
+   The layout is the one dega_hip_lzmh_encode_dev takes as it is: out 16-byte aligned, stride a multiple of 16 (16 ..
+   0x7FFFFFF0).  A channel's text fits when text + 16 bytes <= stride (the room its last, partly filled store needs);
+   one that does not fit gets err[c] = DEGA_ERROR_MEMORY and out_len[c] = 0, the others are unaffected.  Bytes of a row
+   beyond out_len[c] are unspecified.  dega_hip_csv_line_max: the longest line (column - 1 + '-' + 39 digits + '.' +
+   decimals + '\n'; 48 at 6 decimals in column 1); dega_hip_csv_worst_case_bytes: a stride that can never overflow,
+   T x line_max + 16 rounded up to 16 -- six times what two-decimal meter readings need (about 8 bytes per value).
+   Both are pure host code and return 0 for decimals > 6, column 0 or a size beyond size_t.
+   Refused with DEGA_ERROR_INVALID_VALUE before anything is launched: decimals > 6, column 0 (or so many empty columns
+   that no line fits stride), separator_char outside 0 .. 255, a misaligned out or stride, ld < C, null arrays, out
+   overlapping v_tc.  C = 0 or T = 0: nothing is launched, DEGA_OK, lengths 0.
+   The environment variable DEGA_CSV_STORE=8|64 (a measurement and test knob) picks how the kernel stores its text --
+   8-byte stores straight from a register, or 64-byte blocks staged in LDS; the bytes are the same.
+   There is no `decode csv` here (ReadCSV is strtof on arbitrary text: another problem). */
+size_t dega_hip_csv_line_max(unsigned decimals, size_t column);
+size_t dega_hip_csv_worst_case_bytes(size_t T, unsigned decimals, size_t column);
+int dega_hip_csv_write_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column, int separator_char,
+                           uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, void *stream);
+/* The same for host memory, synchronous: chunks of channels are uploaded, rendered and downloaded (as dega_hip_aggregate_host). */
+int dega_hip_csv_write_host(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column, int separator_char,
+                            uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err);
+/* `encode csv # encode lzmh` per channel on `stream`, no synchronisation: the renderer into a text scratch that the
+   context owns (text_stride bytes per channel, as `stride` above), dega_hip_lzmh_encode_dev over it, and a third, tiny
+   launch that hands the renderer's status on (the LZMH kernel, left as it is, would code an overflowed channel as the
+   empty text): a channel whose text outgrows text_stride reports DEGA_ERROR_MEMORY with out_bits 0.  text_stride comes
+   from the caller because the worst case is six times what meter readings need and would not fit the device at
+   64 Ki x 86 400.  out / cap / out_bits / err as dega_hip_lzmh_encode_dev; text_len (may be NULL) receives each channel's
+   text bytes, the denominator of the study's compression ratio.  The scratch follows the protocol of
+   dega_hip_encode_agg_f32_dev's: grow-only by doubling, outgrown blocks kept until the context goes, and a call on
+   another stream than the previous one waits on the device (hipStreamWaitEvent) until that call's last launch has read
+   the text; the host never waits.  There is no `aggregate` in this chain: a -0.0f reading prints -0.00. */
+int dega_hip_lzmh_encode_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column,
+                                 int separator_char, size_t text_stride, uint8_t *out, size_t cap, uint64_t *out_bits, uint64_t *text_len, int32_t *err,
+                                 void *stream);
+/* K x `encode aggregate num_values=N_k # encode csv # encode lzmh`: the passes of dega_hip_aggregate_levels_plan into the
+   aggregate scratch exactly as dega_hip_encode_levels_f32_dev runs them, then per level the renderer, the LZMH encoder
+   and the status launch on the same stream, level k over ceil(T / N_k) sums with text_stride[k] into out[k] (cap[k]
+   bytes per channel) / out_bits[k] / text_len[k] / err[k].  text_len may be NULL, and so may any text_len[k].  The text
+   scratch is sized for the largest level and reused level after level (stream order makes that safe); the aggregate
+   scratch's event is recorded behind the last renderer, the text scratch's behind the last launch.  This entry point
+   means the chain WITH `aggregate` in it: a level with num_values 1 goes through the aggregate kernel like any other
+   (+0.0f + v: a -0.0f reading prints 0.00), unlike dega_hip_encode_levels_f32_dev, where Normalize hides the difference
+   and num_values 1 is coded from the base rows.  Refused before anything is launched: what the calls above refuse, K >
+   DEGA_AGG_MAX_LEVELS, a num_values of 0 or twice, null arrays, two levels' outputs overlapping. */
+int dega_hip_lzmh_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
+                                        unsigned decimals, size_t column, int separator_char, const size_t *text_stride, uint8_t *const *out,
+                                        const size_t *cap, uint64_t *const *out_bits, uint64_t *const *text_len, int32_t *const *err, void *stream);
 
 /* ---- host pointers: the pipelined path DCCLI's stage loop (DCCLI/src/cli.c:430-466) ends up on ---------------------------- */
 /* `samples` and the outputs are HOST memory (pageable or pinned).  The batch is cut into chunks of channels, each on a
