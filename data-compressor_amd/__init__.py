@@ -206,53 +206,40 @@ class _JobCalls:
         device first, as the reference's `encode aggregate` does, and the ceil(T / num_values) sums are coded."""
         import numpy as np
         if num_values != 1:
-            return self._encode_agg_job(x_tc, int(num_values), adaptive, valuesize, samples, factor, packed_cap, channels, packed)
+            # the layout the library is told is the layout the array has: nothing is converted or copied behind the caller's back
+            num_values = int(num_values)
+            assert isinstance(x_tc, np.ndarray) and x_tc.ndim == 2 and x_tc.flags.c_contiguous, "x_tc must be a C-contiguous [T, ld] numpy array"
+            assert samples != SAMPLES_F32 or x_tc.dtype == np.float32, "float32 samples need a float32 array"
+            assert num_values >= 0
+            assert channels is None or 0 <= int(channels) <= x_tc.shape[1], "channels must be at most the row pitch"
+            assert packed is None or (isinstance(packed, np.ndarray) and packed.dtype == np.uint8 and packed.flags.c_contiguous and packed.ndim == 1)
+            rows = library().dega_hip_aggregate_rows(x_tc.shape[0], num_values)
+            return self._encode_packed(self._enc_agg_fn(), (num_values,), "encode_job(num_values=%d)" % num_values, x_tc, rows, adaptive, valuesize,
+                                       samples, factor, packed_cap, channels, packed)
         if not (isinstance(x_tc, np.ndarray) and x_tc.flags.c_contiguous and x_tc.dtype == _sample_dtype(samples)):
             x_tc = np.ascontiguousarray(x_tc, dtype=_sample_dtype(samples))
-        T, pitch = x_tc.shape
-        Cn = pitch if channels is None else int(channels)
-        job = Job(Cn, T, pitch, int(adaptive), int(valuesize), int(samples), float(factor))
-        if packed_cap is None:
-            packed_cap = Cn * (T * 2 + 64)  # generous for meter data; the call says so if it is not
-        offsets = np.zeros(Cn + 1, dtype=np.uint64)
-        bits = np.zeros(Cn, dtype=np.uint64)
-        err = np.zeros(Cn, dtype=np.int32)
-        ret = OK
-        for _ in range(2):
-            buf = packed if packed is not None and packed.size >= packed_cap else np.empty(max(1, packed_cap), dtype=np.uint8)
-            ret = self._enc_fn()(self._handle(), C.byref(job), x_tc.ctypes.data, buf.ctypes.data, packed_cap, offsets.ctypes.data, bits.ctypes.data, err.ctypes.data)
-            if ret != ERROR_MEMORY or int(offsets[Cn]) <= packed_cap:
-                break
-            packed_cap = int(offsets[Cn])
-        self._check(ret, "encode_job")
-        return buf[: int(offsets[Cn])], offsets, bits, err
+        return self._encode_packed(self._enc_fn(), (), "encode_job", x_tc, x_tc.shape[0], adaptive, valuesize, samples, factor, packed_cap, channels, packed)
 
-    def _encode_agg_job(self, x_tc, num_values, adaptive, valuesize, samples, factor, packed_cap, channels, packed):
+    def _encode_packed(self, fn, lead, what, x_tc, rows, adaptive, valuesize, samples, factor, packed_cap, channels, packed):
+        """fn(handle, job, *lead, samples, packed, packed_cap, offsets, bits, err) over x_tc as it is; `rows` values are coded
+        per channel.  A packed_cap that was too small is replaced once by the size the library reports in offsets[C]."""
         import numpy as np
-        # the layout the library is told is the layout the array has: nothing is converted or copied behind the caller's back
-        assert isinstance(x_tc, np.ndarray) and x_tc.ndim == 2 and x_tc.flags.c_contiguous, "x_tc must be a C-contiguous [T, ld] numpy array"
-        assert samples != SAMPLES_F32 or x_tc.dtype == np.float32, "float32 samples need a float32 array"
-        assert num_values >= 0
         T, pitch = x_tc.shape
         Cn = pitch if channels is None else int(channels)
-        assert 0 <= Cn <= pitch, "channels must be at most the row pitch"
-        assert packed is None or (isinstance(packed, np.ndarray) and packed.dtype == np.uint8 and packed.flags.c_contiguous and packed.ndim == 1)
         job = Job(Cn, T, pitch, int(adaptive), int(valuesize), int(samples), float(factor))
-        T_out = library().dega_hip_aggregate_rows(T, num_values)
         if packed_cap is None:
-            packed_cap = Cn * (T_out * 2 + 64)
+            packed_cap = Cn * (rows * 2 + 64)  # generous for meter data; the call says so if it is not
         offsets = np.zeros(Cn + 1, dtype=np.uint64)
         bits = np.zeros(Cn, dtype=np.uint64)
         err = np.zeros(Cn, dtype=np.int32)
         ret = OK
         for _ in range(2):
             buf = packed if packed is not None and packed.size >= packed_cap else np.empty(max(1, packed_cap), dtype=np.uint8)
-            ret = self._enc_agg_fn()(self._handle(), C.byref(job), num_values, x_tc.ctypes.data, buf.ctypes.data, packed_cap, offsets.ctypes.data,
-                                     bits.ctypes.data, err.ctypes.data)
+            ret = fn(self._handle(), C.byref(job), *lead, x_tc.ctypes.data, buf.ctypes.data, packed_cap, offsets.ctypes.data, bits.ctypes.data, err.ctypes.data)
             if ret != ERROR_MEMORY or int(offsets[Cn]) <= packed_cap:
                 break
             packed_cap = int(offsets[Cn])
-        self._check(ret, "encode_job(num_values=%d)" % num_values)
+        self._check(ret, what)
         return buf[: int(offsets[Cn])], offsets, bits, err
 
     def encode_job_levels(self, x_tc, levels, adaptive=1, valuesize=32, factor=100.0, packed_cap=None, channels=None):

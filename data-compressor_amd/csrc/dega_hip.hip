@@ -42,7 +42,7 @@ struct dega_hip_ctx
   std::vector<hipEvent_t> ev_pool; // events handed back by profile_read, reused by the next timed launches
   int force_waves; // 0 = choose by batch size; 4 / 8 = pairs of waves per workgroup, DEGA_WAVES_PER_WORKGROUP (measurement knob)
   Pipeline *pipe;  // streams and buffers of the host-pointer entry points, created on first use
-  // The aggregated rows between the two launches of dega_hip_encode_agg_f32_dev.  The block is shared by all calls on the
+  // The aggregated rows between the launches of dega_hip_encode_levels_f32_dev.  The block is shared by all calls on the
   // context, whatever their streams: agg_done is recorded behind every call's encode launch, and a call on another
   // stream than the last one makes its stream wait for it before its aggregate launch writes the block (on the device;
   // the host never waits).  It grows only, by doubling, and a block it has outgrown is kept until the context goes --
@@ -306,9 +306,6 @@ struct Shape
   size_t C, T, ld;
   int adaptive, valuesize, samples;
   float factor;
-  // host pipeline only: the rows on the host are agg_T fine readings per channel, summed in groups of agg_N on the device
-  // (launch_aggregate) in front of the coder; T is then the aggregated length.  agg_N = 0: no aggregation.
-  size_t agg_N = 0, agg_T = 0;
 };
 
 static int check_job_shape(dega_hip_ctx *ctx, const Shape &j, size_t cap)
@@ -683,32 +680,9 @@ extern "C" int dega_hip_encode_agg_f32_dev(dega_hip_ctx *ctx, const float *v_tc,
     return DEGA_ERROR_INVALID_VALUE;
   if (num_values == 0)
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: num_values must be at least 1 (the reference does not terminate on 0)", hipSuccess);
-  if (num_values == 1) // 0.0f + v differs from v for -0.0f only, and Normalize maps both zeros to 0: the same streams without the pass
-    return dega_hip_encode_f32_dev(ctx, v_tc, C, T, ld, factor, adaptive, valuesize, out, cap, out_bits, err, stream);
-  const size_t T_out = dega_hip_aggregate_rows(T, num_values);
-  const Shape j = shape_of(C, T_out, ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor);
-  int ret;
-  if ((ret = check_job_shape(ctx, j, cap)) != DEGA_OK) // everything the encode launch would refuse, before the first launch
-    return ret;
-  if (C == 0)
-    return DEGA_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  if ((ret = agg_scratch_need(ctx, std::max<size_t>(T_out * ld, 4))) != DEGA_OK)
-    return ret;
-  hipStream_t s = (hipStream_t)stream;
-  if (ctx->agg_done == nullptr)
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->agg_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
-  // the scratch may still be read by the encode launch of an earlier call on another stream: this stream goes on behind it
-  if (ctx->agg_pending && ctx->agg_stream != s)
-    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->agg_done, 0), DEGA_ERROR_LIBRARY_CALL);
-  if ((ret = launch_aggregate(ctx, v_tc, C, T, ld, num_values, ctx->agg_scratch, ld, s)) != DEGA_OK)
-    return ret;
-  ret = launch_encode(ctx, ctx->agg_scratch, j, C, out, cap, out_bits, err, s);
-  // (recorded whatever launch_encode said: the aggregate launch is on the stream and writes the scratch)
-  HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
-  ctx->agg_stream = s;
-  ctx->agg_pending = true;
-  return ret;
+  // one level of the levels form: an aggregate launch into the context's scratch and the coder over it, or, for
+  // num_values = 1, the coder straight over v_tc (0.0f + v differs from v for -0.0f only, and Normalize maps both zeros to 0)
+  return dega_hip_encode_levels_f32_dev(ctx, v_tc, C, T, ld, &num_values, 1, factor, adaptive, valuesize, &out, &cap, &out_bits, &err, stream);
 }
 
 // ---- several granularities from one pass over the base series (aggregate_levels_kernels.hpp) -------------------------------
@@ -978,7 +952,7 @@ extern "C" int dega_hip_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: out, cap, out_bits and err are arrays of K entries", hipSuccess);
   int ret;
   // every level's encode launch judged before the first launch (cap[k] and the 2^25 limit against level k's rows), and
-  // the levels that are summed (N = 1 is coded straight from v_tc, as dega_hip_encode_agg_f32_dev does)
+  // the levels that are summed (N = 1 is coded straight from v_tc)
   Shape j[AGG_MAX_LEVELS];
   size_t N[AGG_MAX_LEVELS], off[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, n = 0;
   for (size_t k = 0; k < K; k++)
@@ -1011,7 +985,8 @@ extern "C" int dega_hip_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_
   hipStream_t s = (hipStream_t)stream;
   if (ctx->agg_done == nullptr)
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->agg_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
-  if (ctx->agg_pending && ctx->agg_stream != s) // the protocol of dega_hip_encode_agg_f32_dev
+  // the scratch may still be read by the encode launch of an earlier call on another stream: this stream goes on behind it
+  if (ctx->agg_pending && ctx->agg_stream != s)
     HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->agg_done, 0), DEGA_ERROR_LIBRARY_CALL);
   if ((ret = launch_aggregate_levels(ctx, v_tc, C, T, ld, N, n, a, ldo, s)) == DEGA_OK)
   {

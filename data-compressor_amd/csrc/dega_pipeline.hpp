@@ -378,7 +378,7 @@ struct Slot
 {
   hipStream_t s = nullptr;
   GrowDev a, b, meta; // encode: a = samples, then the packed streams; b = slabs.  decode: a = packed streams, b = slabs, c = samples
-  GrowDev c;          // (encode with aggregation in front: c = the fine readings as uploaded, a = their sums, which the coder reads)
+  GrowDev c;          // (encode at coarser granularities: c = the fine readings as uploaded, later the packed streams; a = the levels' sums)
   GrowPin hmeta, stage;
   // few, long channels: encode uploads the rows in bands and codes every band as it lands (one launch per band, the lanes'
   // state saved in between: EncodeArgs::seg_state); decode downloads in bands beside the running kernel.  The copies'
@@ -543,6 +543,46 @@ static ChunkPlan plan_chunks(size_t C, size_t bytes_per_channel_in, size_t bytes
   return p;
 }
 
+// Chunk k of a share of C channels: its channels [c0, c0 + n) and the slot it runs on
+struct Chunk
+{
+  size_t c0 = 0, n = 0;
+  int slot = 0;
+  void place(const ChunkPlan &plan, size_t C, size_t k)
+  {
+    c0 = k * plan.chunk_channels;
+    n = std::min(plan.chunk_channels, C - c0);
+    slot = (int)(k % (size_t)plan.nslots);
+  }
+};
+
+// The software pipeline over a share's chunks: the first stage of chunk k is enqueued `ahead` chunks before the second
+// stage of the same chunk.  Chunk k + nslots reuses the slot of chunk k, so ahead <= nslots and the second stage of
+// chunk k - ahead goes BEFORE the first stage of chunk k: a slot is reused only after its previous chunk's second stage.
+template <class Stage1, class Stage2>
+static int run_chunks(size_t nchunks, size_t ahead, Stage1 stage1, Stage2 stage2)
+{
+  int ret;
+  for (size_t k = 0; k < nchunks + ahead; k++)
+  {
+    if (k >= ahead && (ret = stage2(k - ahead)) != DEGA_OK)
+      return ret;
+    if (k < nchunks && (ret = stage1(k)) != DEGA_OK)
+      return ret;
+  }
+  return DEGA_OK;
+}
+
+// everything the chunks left in flight: the staging ring's downloads to their place, then the slots' streams
+static int finish_slots(dega_hip_ctx *ctx, Pipeline *pl, int nslots)
+{
+  HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
+  for (int s = 0; s < nslots; s++)
+    if (pl->slot[s].s != nullptr)
+      HIP_TRY(ctx, hipStreamSynchronize(pl->slot[s].s), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
 // Rows per band when a chunk's samples cross the link in bands (0: in one piece, the usual way): encode codes every band
 // with a launch of its own as soon as it has landed -- plain stream order, an event per band; nothing on the device ever
 // waits for the host -- and decode sends every band home as soon as all waves have stored it.  Worth it when the channels
@@ -578,10 +618,8 @@ struct EncodeSink
   int32_t *err = nullptr;
 };
 
-struct EncChunk
+struct EncChunk : Chunk
 {
-  size_t c0 = 0, n = 0;
-  int slot = 0;
   uint64_t total = 0; // packed bytes of the chunk
   bool gathered = false, redone = false;
   bool bands = false; // its rows went up in bands, each coded by a launch of its own
@@ -642,12 +680,18 @@ static int encode_redo_chunk(dega_hip_ctx *ctx, Pipeline *pl, Slot &sl, const Sh
   return DEGA_OK;
 }
 
-// DEGA_PIPELINE_AHEAD=n: chunks whose first stage is enqueued before the oldest one's second stage (default 2; measurement)
-static size_t stages_ahead()
+// How far an encode call's first stages run ahead of the second ones (DEGA_PIPELINE_AHEAD=n: measurement; default 2).
+// Not as far as the slots would allow: HIP puts the streams on a few hardware queues, and a queue takes its packets in
+// order -- with all eight chunks' first stages enqueued up front, chunk 0's gather and download (enqueued when its sizes
+// were on the host, 7 ms into the call) sat behind the launches of a later chunk that were still waiting for their
+// bands, and went out at 46 ms; every chunk's streams came home after the last upload (trace of 65 536 x 10 800,
+// tools/e2eprof.sh; 66 ms a call). Two chunks ahead keep the link busy (enqueueing a chunk takes 0.15 ms) and a
+// download waits for one chunk's launches at most.
+static size_t stages_ahead(const ChunkPlan &plan)
 {
   const char *e = getenv("DEGA_PIPELINE_AHEAD");
   const long v = e != nullptr ? atol(e) : 2;
-  return (size_t)(v < 1 ? 1 : v);
+  return std::min<size_t>((size_t)std::max(plan.nslots, 1), (size_t)(v < 1 ? 1 : v));
 }
 
 static bool decode_uploads_first() // DEGA_PIPELINE_UPLOADS_FIRST=0: upload and kernel enqueued chunk by chunk (measurement)
@@ -681,26 +725,21 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, 
     return ret;
   const size_t esz = sample_bytes(j);
   const size_t cap = usual_cap(j);
-  // aggregation in front of the coder (Shape::agg_N): agg_T rows cross the link, T of them are coded; a slot holds both
-  const bool agg = j.agg_N != 0;
-  const size_t rows_in = agg ? j.agg_T : j.T;
-  const size_t dev_per_channel = std::max(j.T * esz + 64, cap) + 16 + cap + 64 + (agg ? rows_in * esz + 64 : 0);
-  const ChunkPlan plan = plan_chunks(j.C, rows_in * esz, dev_per_channel, deliver ? 0 : 1);
+  const size_t dev_per_channel = std::max(j.T * esz + 64, cap) + 16 + cap + 64;
+  const ChunkPlan plan = plan_chunks(j.C, j.T * esz, dev_per_channel, deliver ? 0 : 1);
   if (plan.nslots < 0)
     return fail(ctx, DEGA_ERROR_MEMORY, "the device's share of the batch does not fit its memory", hipSuccess);
   run.chunks.assign(plan.nchunks, EncChunk());
   run.total = 0;
   bool out_full = false;
   const bool samples_pinned = is_pinned(samples), packed_pinned = is_pinned(sink.packed);
-  const bool in_place = samples_pinned && read_in_place() && !agg;
+  const bool in_place = samples_pinned && read_in_place();
 
   TRACE("encode share: C %zu T %zu, %zu chunks of %zu channels, %d slots", j.C, j.T, plan.nchunks, plan.chunk_channels, plan.nslots);
   auto stage1 = [&](size_t k) -> int {
     EncChunk &ch = run.chunks[k];
     TRACE("chunk %zu stage1 begin", k);
-    ch.c0 = k * plan.chunk_channels;
-    ch.n = std::min(plan.chunk_channels, j.C - ch.c0);
-    ch.slot = (int)(k % (size_t)plan.nslots);
+    ch.place(plan, j.C, k);
     Slot &sl = pl->slot[ch.slot];
     int r;
     if ((r = slot_stream(ctx, sl)) != DEGA_OK)
@@ -714,7 +753,7 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, 
     cj.C = ch.n;
     cj.ld = ch.n;
     const uint8_t *const src = (const uint8_t *)samples + ch.c0 * esz;
-    const size_t band_rows = agg ? 0 : band_rows_of(plan, j, ch.n * esz);
+    const size_t band_rows = band_rows_of(plan, j, ch.n * esz);
     ch.rows = (const uint8_t *)sl.a.p;
     ch.rows_ld = ch.n;
     void *dev_src = nullptr;
@@ -723,19 +762,7 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, 
       (void)hipGetLastError(); // (pinned, but not mapped into the device's address space: the copy engine takes it)
       dev_src = nullptr;
     }
-    if (agg)
-    {
-      // Whole-chunk launches behind a copy-engine upload: the chunk's columns of all agg_T fine rows, their sums in
-      // groups of agg_N (per channel, so a chunk of channels is self-contained), then the coder over the T sums.  The
-      // link carries agg_N times what the coder sees and is the bound; no bands, no in-place read of pinned rows.
-      HIP_TRY(ctx, sl.c.need(ch.n * j.agg_T * esz + 64), DEGA_ERROR_MEMORY);
-      HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, src, j.ld * esz, ch.n * esz, j.agg_T, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
-      if ((r = launch_aggregate(ctx, (const float *)sl.c.p, ch.n, j.agg_T, ch.n, j.agg_N, (float *)sl.a.p, ch.n, sl.s)) != DEGA_OK)
-        return r;
-      if ((r = launch_encode(ctx, sl.a.p, cj, j.C, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
-        return r;
-    }
-    else if (dev_src != nullptr)
+    if (dev_src != nullptr)
     {
       // The caller's array is pinned and the chunk is all of its columns: the kernel's filling waves fetch their rows
       // from it themselves (LDS-DMA over the link, 256-byte row segments: 8 192 x 86 400 in 65.2 ms against 66.5 ms
@@ -876,26 +903,11 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, 
     return DEGA_OK;
   };
 
-  // chunk k + nslots reuses the slot of chunk k: its second stage has to be enqueued first
-  // How far the first stages run ahead of the second ones.  Not as far as the slots would allow: HIP puts the streams
-  // on a few hardware queues, and a queue takes its packets in order -- with all eight chunks' first stages enqueued up
-  // front, chunk 0's gather and download (enqueued when its sizes were on the host, 7 ms into the call) sat behind the
-  // launches of a later chunk that were still waiting for their bands, and went out at 46 ms; every chunk's streams
-  // came home after the last upload (trace of 65 536 x 10 800, gpurun_out/e2eprof; 66 ms a call).  Two chunks ahead
-  // keep the link busy (enqueueing a chunk takes 0.15 ms) and a download waits for one chunk's launches at most.
-  const size_t ahead = std::min<size_t>((size_t)plan.nslots, stages_ahead());
-  for (size_t k = 0; k < plan.nchunks + ahead; k++)
-  {
-    if (k >= ahead && (ret = stage2(k - ahead)) != DEGA_OK)
-      return ret;
-    if (k < plan.nchunks && (ret = stage1(k)) != DEGA_OK)
-      return ret;
-  }
+  if ((ret = run_chunks(plan.nchunks, stages_ahead(plan), stage1, stage2)) != DEGA_OK)
+    return ret;
   TRACE("all chunks enqueued");
-  HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
-  for (int s = 0; s < plan.nslots; s++)
-    if (pl->slot[s].s != nullptr)
-      HIP_TRY(ctx, hipStreamSynchronize(pl->slot[s].s), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = finish_slots(ctx, pl, plan.nslots)) != DEGA_OK)
+    return ret;
   TRACE("encode share done");
   if (sink.offsets != nullptr)
     sink.offsets[j.C] = run.total;
@@ -946,10 +958,12 @@ static size_t meta_stride(size_t n) // the K MetaViews of a slot lie one behind 
   return (MetaView::bytes(n) + 7) & ~(size_t)7;
 }
 
-// One device's share of a batch coded at K granularities.  A function of its own beside encode_share (whose paths stay
-// as they are), with its habits: chunks of channels on the slots' streams, nothing allocated per call beyond growing the
-// slot's buffers, only stream bytes come back, first stages two chunks ahead, a level of a chunk whose stream outgrows
-// the usual slab redone with worst-case slabs.  A chunk's fine rows cross the link ONCE; a slot holds them (c), the sums
+// One device's share of a batch coded at K granularities (K = 1: the single-level aggregated forms).  A function of its
+// own beside encode_share, which codes the rows as they are, with its habits: chunks of channels on the slots' streams,
+// nothing allocated per call beyond growing the slot's buffers, only stream bytes come back, first stages two chunks
+// ahead, a level of a chunk whose stream outgrows the usual slab redone with worst-case slabs.  Whole-chunk launches
+// behind a copy-engine upload: the link carries the fine rows, N times what a level's coder sees, and is the bound; no
+// bands, no in-place read of pinned rows.  A chunk's fine rows cross the link ONCE; a slot holds them (c), the sums
 // of all summed levels (a), K slab regions (b) and K sets of the small arrays (meta).  When the K encode launches of a
 // chunk are done its fine rows are no longer needed, and their buffer takes the packed streams, level behind level.
 // j: C, ld, factor, adaptive, valuesize of the job; j.T the FINE length.  Always delivers (no resident phase).
@@ -980,10 +994,8 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &j, const size_t *
   const size_t fine_bytes = std::max(j.T * esz + 64, cap_sum); // per channel: the fine rows, later every level's packed streams
   const size_t dev_per_channel = fine_bytes + 16 + sum_rows * esz + 16 * K + cap_sum + 64 + K * 32;
   const ChunkPlan plan = plan_chunks(j.C, j.T * esz, dev_per_channel, 0);
-  struct LevelChunk
+  struct LevelChunk : Chunk
   {
-    size_t c0 = 0, n = 0;
-    int slot = 0;
     EncChunk lv[AGG_MAX_LEVELS]; // per level: rows / rows_ld / total / redone / redo_bytes
   };
   std::vector<LevelChunk> chunks(plan.nchunks);
@@ -995,9 +1007,7 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &j, const size_t *
 
   auto stage1 = [&](size_t q) -> int {
     LevelChunk &ch = chunks[q];
-    ch.c0 = q * plan.chunk_channels;
-    ch.n = std::min(plan.chunk_channels, j.C - ch.c0);
-    ch.slot = (int)(q % (size_t)plan.nslots);
+    ch.place(plan, j.C, q);
     Slot &sl = pl->slot[ch.slot];
     int r;
     if ((r = slot_stream(ctx, sl)) != DEGA_OK)
@@ -1110,18 +1120,8 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &j, const size_t *
     return DEGA_OK;
   };
 
-  const size_t ahead = std::min<size_t>((size_t)std::max(plan.nslots, 1), stages_ahead());
-  for (size_t q = 0; q < plan.nchunks + ahead; q++)
-  {
-    if (q >= ahead && q - ahead < plan.nchunks && (ret = stage2(q - ahead)) != DEGA_OK)
-      return ret;
-    if (q < plan.nchunks && (ret = stage1(q)) != DEGA_OK)
-      return ret;
-  }
-  HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
-  for (int s = 0; s < plan.nslots; s++)
-    if (pl->slot[s].s != nullptr)
-      HIP_TRY(ctx, hipStreamSynchronize(pl->slot[s].s), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = run_chunks(plan.nchunks, stages_ahead(plan), stage1, stage2)) != DEGA_OK || (ret = finish_slots(ctx, pl, plan.nslots)) != DEGA_OK)
+    return ret;
   bool any_full = false;
   sized = true;
   for (size_t k = 0; k < K; k++)
@@ -1155,10 +1155,8 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed
   // few of them side by side, and the rows go home in bands beside the running kernel anyway (65 536 x 10 800 from
   // pinned memory: 8 chunks 83 ms, 4: 63 ms, 2: 66.5 ms, 1: 66 ms).
   const ChunkPlan plan = plan_chunks(j.C, j.T * osz, dev_per_channel, 0, 4);
-  struct DecChunk
+  struct DecChunk : Chunk
   {
-    size_t c0, n;
-    int slot;
     size_t band_rows; // 0: the samples come home after the kernel; else in bands of rows beside it
     size_t cap;       // slab bytes per channel
   };
@@ -1170,9 +1168,7 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed
   // first stage, part a: the chunk's packed streams go up and are spread into slabs
   auto stage1a = [&](size_t k) -> int {
     DecChunk &ch = chunks[k];
-    ch.c0 = k * plan.chunk_channels;
-    ch.n = std::min(plan.chunk_channels, j.C - ch.c0);
-    ch.slot = (int)(k % (size_t)plan.nslots);
+    ch.place(plan, j.C, k);
     Slot &sl = pl->slot[ch.slot];
     int r;
     if ((r = slot_stream(ctx, sl)) != DEGA_OK)
@@ -1314,15 +1310,11 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed
         return ret;
     return DEGA_OK;
   }
-  const size_t ahead = std::min<size_t>((size_t)plan.nslots, decode_stages_ahead());
-  for (size_t k = 0; k < plan.nchunks + ahead; k++)
-  {
-    if (k >= ahead && (ret = stage2(k - ahead)) != DEGA_OK)
-      return ret;
-    if (k < plan.nchunks && ((ret = stage1a(k)) != DEGA_OK || (ret = stage1b(k)) != DEGA_OK))
-      return ret;
-  }
-  return DEGA_OK;
+  auto stage1 = [&](size_t k) -> int {
+    const int r = stage1a(k);
+    return r != DEGA_OK ? r : stage1b(k);
+  };
+  return run_chunks(plan.nchunks, std::min<size_t>((size_t)plan.nslots, decode_stages_ahead()), stage1, stage2);
 }
 
 static int check_packed_input(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed, const uint64_t *offsets, const uint64_t *bits)
@@ -1463,6 +1455,51 @@ static int group_fail(dega_hip_group *g, int code, dega_hip_ctx *c, size_t dev_i
   return code;
 }
 
+// work(g) for every member g < G, each on a host thread of its own (in the caller's when there is one member); the
+// first member that failed is the call's failure
+template <class Work>
+static int on_members(dega_hip_group *grp, size_t G, Work work)
+{
+  std::vector<int> rets(G, DEGA_OK);
+  if (G == 1)
+    rets[0] = work((size_t)0);
+  else
+  {
+    std::vector<std::thread> th;
+    for (size_t g = 0; g < G; g++)
+      th.emplace_back([&, g] { rets[g] = work(g); });
+    for (std::thread &t : th)
+      t.join();
+  }
+  for (size_t g = 0; g < G; g++)
+    if (rets[g] != DEGA_OK)
+      return group_fail(grp, rets[g], grp->ctx[g], g);
+  return DEGA_OK;
+}
+
+// the group of the single-context (`*_host`) forms: the caller's context alone
+static dega_hip_group group_of_one(dega_hip_ctx *ctx)
+{
+  dega_hip_group one;
+  one.ctx.push_back(ctx);
+  one.last_error[0] = '\0';
+  return one;
+}
+
+// the packed form of a call's outputs, from the ABI's arguments (offsets[0] = 0 is written here, once)
+static EncodeSink packed_sink(uint8_t *packed, size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err)
+{
+  EncodeSink sink;
+  sink.packed = packed;
+  sink.packed_cap = packed_cap;
+  sink.offsets = offsets;
+  sink.bits = out_bits;
+  sink.err = err;
+  if (offsets != nullptr)
+    offsets[0] = 0;
+  return sink;
+}
+
 static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samples, const EncodeSink &sink)
 {
   if (grp == nullptr || grp->ctx.empty())
@@ -1495,7 +1532,7 @@ static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samp
     }
     free_b = std::min(free_b, f);
   }
-  const size_t per_channel = std::max(j.T * esz + 64, usual_cap(j)) + 16 + usual_cap(j) + 64 + 256 + (j.agg_N != 0 ? j.agg_T * esz + 64 : 0);
+  const size_t per_channel = std::max(j.T * esz + 64, usual_cap(j)) + 16 + usual_cap(j) + 64 + 256;
   size_t round_channels = std::max<size_t>(G * 512, std::min<size_t>(j.C, free_b / 10 * 6 / per_channel * G / 512 * 512));
   uint64_t base = 0;
   bool out_full = false;
@@ -1551,31 +1588,23 @@ static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samp
       r0 += rC;
       continue; // keep sizing
     }
-    th.clear();
-    std::vector<std::vector<uint8_t>> tmp(G);
-    for (size_t g = 0; g < G; g++)
-      th.emplace_back([&, g] {
-        if (sink.slabs != nullptr)
-        {
-          tmp[g].resize((size_t)runs[g].total + 1);
-          rets[g] = encode_deliver(grp->ctx[g], runs[g], tmp[g].data(), 0);
-          for (size_t i = 0; rets[g] == DEGA_OK && i < cut[g + 1] - cut[g]; i++)
-          {
-            const size_t c = r0 + cut[g] + i, nb = (size_t)(rel[g][i + 1] - rel[g][i]);
-            if (nb > sink.slab_cap)
-              sink.err[c] = sink.err[c] == DEGA_OK ? DEGA_ERROR_MEMORY : sink.err[c];
-            if (nb > 0)
-              memcpy(sink.slabs + c * sink.slab_cap, tmp[g].data() + rel[g][i], std::min(nb, sink.slab_cap));
-          }
-        }
-        else
-          rets[g] = encode_deliver(grp->ctx[g], runs[g], sink.packed, dev_base[g]);
-      });
-    for (std::thread &t : th)
-      t.join();
-    for (size_t g = 0; g < G; g++)
-      if (rets[g] != DEGA_OK)
-        return group_fail(grp, rets[g], grp->ctx[g], g);
+    ret = on_members(grp, G, [&](size_t g) -> int {
+      if (sink.slabs == nullptr)
+        return encode_deliver(grp->ctx[g], runs[g], sink.packed, dev_base[g]);
+      std::vector<uint8_t> tmp((size_t)runs[g].total + 1);
+      const int r = encode_deliver(grp->ctx[g], runs[g], tmp.data(), 0);
+      for (size_t i = 0; r == DEGA_OK && i < cut[g + 1] - cut[g]; i++)
+      {
+        const size_t c = r0 + cut[g] + i, nb = (size_t)(rel[g][i + 1] - rel[g][i]);
+        if (nb > sink.slab_cap)
+          sink.err[c] = sink.err[c] == DEGA_OK ? DEGA_ERROR_MEMORY : sink.err[c];
+        if (nb > 0)
+          memcpy(sink.slabs + c * sink.slab_cap, tmp.data() + rel[g][i], std::min(nb, sink.slab_cap));
+      }
+      return r;
+    });
+    if (ret != DEGA_OK)
+      return ret;
     r0 += rC;
   }
   if (sink.offsets != nullptr)
@@ -1601,27 +1630,12 @@ static int decode_on_group(dega_hip_group *grp, const Shape &j, const uint8_t *p
   const size_t G = std::max<size_t>(1, std::min<size_t>(grp->ctx.size(), (j.C + 511) / 512));
   const size_t osz = sample_bytes(j);
   const std::vector<size_t> cut = split_channels(j.C, G);
-  std::vector<int> rets(G, DEGA_OK);
-  auto work = [&](size_t g) {
+  return on_members(grp, G, [&](size_t g) -> int {
     Shape sj = j;
     sj.C = cut[g + 1] - cut[g];
-    rets[g] = decode_share(grp->ctx[g], sj, packed, offsets + cut[g], bits + cut[g], (uint8_t *)samples + cut[g] * osz,
-                           out_count != nullptr ? out_count + cut[g] : nullptr, err + cut[g]);
-  };
-  if (G == 1)
-    work(0);
-  else
-  {
-    std::vector<std::thread> th;
-    for (size_t g = 0; g < G; g++)
-      th.emplace_back(work, g);
-    for (std::thread &t : th)
-      t.join();
-  }
-  for (size_t g = 0; g < G; g++)
-    if (rets[g] != DEGA_OK)
-      return group_fail(grp, rets[g], grp->ctx[g], g);
-  return DEGA_OK;
+    return decode_share(grp->ctx[g], sj, packed, offsets + cut[g], bits + cut[g], (uint8_t *)samples + cut[g] * osz,
+                        out_count != nullptr ? out_count + cut[g] : nullptr, err + cut[g]);
+  });
 }
 
 extern "C" int dega_hip_group_encode(dega_hip_group *grp, const dega_hip_job *job, const void *samples, uint8_t *packed, size_t packed_cap,
@@ -1629,51 +1643,7 @@ extern "C" int dega_hip_group_encode(dega_hip_group *grp, const dega_hip_job *jo
 {
   if (job == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
-  EncodeSink sink;
-  sink.packed = packed;
-  sink.packed_cap = packed_cap;
-  sink.offsets = offsets;
-  sink.bits = out_bits;
-  sink.err = err;
-  if (offsets != nullptr)
-    offsets[0] = 0;
-  return encode_on_group(grp, shape_from_job(job), samples, sink);
-}
-
-// the job of the aggregated forms: float32 samples only; job->T fine readings per channel, coded as ceil(T / num_values) sums
-static int agg_job_shape(const dega_hip_job *job, size_t num_values, Shape &j)
-{
-  if (job == nullptr || num_values == 0 || job->samples != DEGA_SAMPLES_F32)
-    return DEGA_ERROR_INVALID_VALUE;
-  j = shape_from_job(job);
-  if (num_values > 1) // 1: the plain call (the same streams: Normalize maps both zeros to 0)
-  {
-    j.agg_N = num_values;
-    j.agg_T = job->T;
-    j.T = dega_hip_aggregate_rows(job->T, num_values);
-  }
-  return DEGA_OK;
-}
-
-extern "C" int dega_hip_group_encode_agg(dega_hip_group *grp, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
-                                         size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err)
-{
-  Shape j;
-  if (grp == nullptr)
-    return DEGA_ERROR_INVALID_VALUE;
-  if (agg_job_shape(job, num_values, j) != DEGA_OK || offsets == nullptr)
-  {
-    snprintf(grp->last_error, sizeof(grp->last_error), "encode_agg: num_values must be at least 1 and the job's samples DEGA_SAMPLES_F32");
-    return DEGA_ERROR_INVALID_VALUE;
-  }
-  EncodeSink sink;
-  sink.packed = packed;
-  sink.packed_cap = packed_cap;
-  sink.offsets = offsets;
-  sink.bits = out_bits;
-  sink.err = err;
-  offsets[0] = 0;
-  return encode_on_group(grp, j, samples, sink);
+  return encode_on_group(grp, shape_from_job(job), samples, packed_sink(packed, packed_cap, offsets, out_bits, err));
 }
 
 extern "C" int dega_hip_group_decode(dega_hip_group *grp, const dega_hip_job *job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits,
@@ -1690,9 +1660,7 @@ static int encode_on_ctx(dega_hip_ctx *ctx, const Shape &j, const void *samples,
 {
   if (ctx == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
-  dega_hip_group one;
-  one.ctx.push_back(ctx);
-  one.last_error[0] = '\0';
+  dega_hip_group one = group_of_one(ctx);
   return encode_on_group(&one, j, samples, sink);
 }
 
@@ -1701,9 +1669,7 @@ static int decode_on_ctx(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packe
 {
   if (ctx == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
-  dega_hip_group one;
-  one.ctx.push_back(ctx);
-  one.last_error[0] = '\0';
+  dega_hip_group one = group_of_one(ctx);
   return decode_on_group(&one, j, packed, offsets, bits, samples, out_count, err);
 }
 
@@ -1712,34 +1678,7 @@ extern "C" int dega_hip_encode_job_host(dega_hip_ctx *ctx, const dega_hip_job *j
 {
   if (job == nullptr || offsets == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
-  EncodeSink sink;
-  sink.packed = packed;
-  sink.packed_cap = packed_cap;
-  sink.offsets = offsets;
-  sink.bits = out_bits;
-  sink.err = err;
-  offsets[0] = 0;
-  return encode_on_ctx(ctx, shape_from_job(job), samples, sink);
-}
-
-extern "C" int dega_hip_encode_agg_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
-                                            size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err)
-{
-  Shape j;
-  if (ctx == nullptr)
-    return DEGA_ERROR_INVALID_VALUE;
-  if (agg_job_shape(job, num_values, j) != DEGA_OK)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode_agg: num_values must be at least 1 and the job's samples DEGA_SAMPLES_F32", hipSuccess);
-  if (offsets == nullptr)
-    return DEGA_ERROR_INVALID_VALUE;
-  EncodeSink sink;
-  sink.packed = packed;
-  sink.packed_cap = packed_cap;
-  sink.offsets = offsets;
-  sink.bits = out_bits;
-  sink.err = err;
-  offsets[0] = 0;
-  return encode_on_ctx(ctx, j, samples, sink);
+  return encode_on_ctx(ctx, shape_from_job(job), samples, packed_sink(packed, packed_cap, offsets, out_bits, err));
 }
 
 // ---- K granularities from one upload ---------------------------------------------------------------------------------------
@@ -1803,11 +1742,9 @@ static int encode_levels_on_group(dega_hip_group *grp, const dega_hip_job *job, 
   // buffer of its own (no larger than the caller's: a share that does not fit there does not fit the call), and the
   // caller's packed[k] is filled by host-side copies once the sizes in front are known.
   const std::vector<size_t> cut = split_channels(j.C, G);
-  std::vector<int> rets(G, DEGA_OK), sized(G, 0);
   std::vector<std::vector<LevelSink>> sinks(G, std::vector<LevelSink>(K));
   std::vector<std::vector<std::unique_ptr<uint8_t[]>>> tmp(G);
   std::vector<std::vector<std::vector<uint64_t>>> rel(G, std::vector<std::vector<uint64_t>>(K));
-  std::vector<std::thread> th;
   for (size_t g = 0; g < G; g++)
   {
     tmp[g].resize(K);
@@ -1826,36 +1763,34 @@ static int encode_levels_on_group(dega_hip_group *grp, const dega_hip_job *job, 
       s.bits = out_bits[k] + cut[g];
       s.err = err[k] + cut[g];
     }
-    th.emplace_back([&, g, n] {
-      Shape sj = j;
-      sj.C = n;
-      const void *const src = (const uint8_t *)samples + cut[g] * sizeof(float);
-      bool ok_sized = false;
-      rets[g] = encode_levels_share(grp->ctx[g], sj, num_values, K, src, sinks[g].data(), ok_sized);
-      // A level that outgrew the member's buffer but fits the caller's (a chunk redone with worst-case slabs): once more,
-      // with what it asked for.  Decided level by level: a level that does not fit the caller's buffer either stays
-      // sized only, and the others are still delivered.
-      bool retry = false;
-      for (size_t k = 0; k < K && rets[g] == DEGA_ERROR_MEMORY && ok_sized; k++)
-        if (sinks[g][k].full && sinks[g][k].total <= packed_cap[k])
-        {
-          tmp[g][k].reset(new uint8_t[(size_t)sinks[g][k].total + 1]);
-          sinks[g][k].packed = tmp[g][k].get();
-          sinks[g][k].packed_cap = (size_t)sinks[g][k].total;
-          retry = true;
-        }
-      if (retry)
-        rets[g] = encode_levels_share(grp->ctx[g], sj, num_values, K, src, sinks[g].data(), ok_sized);
-      sized[g] = ok_sized ? 1 : 0;
-    });
   }
-  for (std::thread &t : th)
-    t.join();
-  // any failure of a member is the call's, as in encode_on_group; DEGA_ERROR_MEMORY is "a packed buffer is too small" only
-  // where the member sized all its channels -- otherwise an allocation failed and its outputs are incomplete
-  for (size_t g = 0; g < G; g++)
-    if (rets[g] != DEGA_OK && !(rets[g] == DEGA_ERROR_MEMORY && sized[g] != 0))
-      return group_fail(grp, rets[g], grp->ctx[g], g);
+  ret = on_members(grp, G, [&](size_t g) -> int {
+    Shape sj = j;
+    sj.C = cut[g + 1] - cut[g];
+    const void *const src = (const uint8_t *)samples + cut[g] * sizeof(float);
+    bool sized = false;
+    int r = encode_levels_share(grp->ctx[g], sj, num_values, K, src, sinks[g].data(), sized);
+    // A level that outgrew the member's buffer but fits the caller's (a chunk redone with worst-case slabs): once more,
+    // with what it asked for.  Decided level by level: a level that does not fit the caller's buffer either stays
+    // sized only, and the others are still delivered.
+    bool retry = false;
+    for (size_t k = 0; k < K && r == DEGA_ERROR_MEMORY && sized; k++)
+      if (sinks[g][k].full && sinks[g][k].total <= packed_cap[k])
+      {
+        tmp[g][k].reset(new uint8_t[(size_t)sinks[g][k].total + 1]);
+        sinks[g][k].packed = tmp[g][k].get();
+        sinks[g][k].packed_cap = (size_t)sinks[g][k].total;
+        retry = true;
+      }
+    if (retry)
+      r = encode_levels_share(grp->ctx[g], sj, num_values, K, src, sinks[g].data(), sized);
+    // any failure of a member is the call's, as in encode_on_group; DEGA_ERROR_MEMORY is "a packed buffer is too small"
+    // only where the member sized all its channels (its levels' `full` say which) -- otherwise an allocation failed and
+    // its outputs are incomplete
+    return r == DEGA_ERROR_MEMORY && sized ? DEGA_OK : r;
+  });
+  if (ret != DEGA_OK)
+    return ret;
   bool any_full = false;
   for (size_t k = 0; k < K; k++)
   {
@@ -1907,10 +1842,55 @@ extern "C" int dega_hip_encode_levels_job_host(dega_hip_ctx *ctx, const dega_hip
   const char *what;
   if (check_levels_job(job, num_values, K, samples, packed, packed_cap, offsets, out_bits, err, &what) != DEGA_OK)
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, what, hipSuccess);
-  dega_hip_group one;
-  one.ctx.push_back(ctx);
-  one.last_error[0] = '\0';
+  dega_hip_group one = group_of_one(ctx);
   return encode_levels_on_group(&one, job, num_values, K, samples, packed, packed_cap, offsets, out_bits, err);
+}
+
+// ---- one coarser granularity: the levels call with K = 1 -------------------------------------------------------------------
+
+// the arguments of the two single-level forms; `what` gets the reason of a refusal
+static int check_agg_job(const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed, size_t packed_cap, uint64_t *offsets,
+                         uint64_t *out_bits, int32_t *err, const char **what)
+{
+  *what = "encode_agg: num_values must be at least 1 and the job's samples DEGA_SAMPLES_F32";
+  if (job == nullptr || num_values == 0 || job->samples != DEGA_SAMPLES_F32 || offsets == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  return num_values == 1 ? DEGA_OK : check_levels_job(job, &num_values, 1, samples, &packed, &packed_cap, &offsets, &out_bits, &err, what);
+}
+
+// num_values = 1 is the plain call (the same streams: Normalize maps both zeros to 0), with its in-place and band paths
+static int encode_agg_on_group(dega_hip_group *grp, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed, size_t packed_cap,
+                               uint64_t *offsets, uint64_t *out_bits, int32_t *err)
+{
+  if (num_values == 1)
+    return encode_on_group(grp, shape_from_job(job), samples, packed_sink(packed, packed_cap, offsets, out_bits, err));
+  return encode_levels_on_group(grp, job, &num_values, 1, samples, &packed, &packed_cap, &offsets, &out_bits, &err);
+}
+
+extern "C" int dega_hip_group_encode_agg(dega_hip_group *grp, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
+                                         size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err)
+{
+  if (grp == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  const char *what;
+  if (check_agg_job(job, num_values, samples, packed, packed_cap, offsets, out_bits, err, &what) != DEGA_OK)
+  {
+    snprintf(grp->last_error, sizeof(grp->last_error), "%s", what);
+    return DEGA_ERROR_INVALID_VALUE;
+  }
+  return encode_agg_on_group(grp, job, num_values, samples, packed, packed_cap, offsets, out_bits, err);
+}
+
+extern "C" int dega_hip_encode_agg_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
+                                            size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  const char *what;
+  if (check_agg_job(job, num_values, samples, packed, packed_cap, offsets, out_bits, err, &what) != DEGA_OK)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, what, hipSuccess);
+  dega_hip_group one = group_of_one(ctx);
+  return encode_agg_on_group(&one, job, num_values, samples, packed, packed_cap, offsets, out_bits, err);
 }
 
 // float32 rows in host memory -> their sums in host memory, synchronous: chunks of channels through the context's first
@@ -2080,14 +2060,7 @@ extern "C" int dega_hip_encode_packed_host(dega_hip_ctx *ctx, const int32_t *x_t
     return ret;
   if (offsets == nullptr || out_bits == nullptr || err == nullptr || (packed == nullptr && packed_cap != 0))
     return DEGA_ERROR_INVALID_VALUE;
-  EncodeSink sink;
-  sink.packed = packed;
-  sink.packed_cap = packed_cap;
-  sink.offsets = offsets;
-  sink.bits = out_bits;
-  sink.err = err;
-  offsets[0] = 0;
-  return encode_on_ctx(ctx, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_I32), x_tc, sink);
+  return encode_on_ctx(ctx, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_I32), x_tc, packed_sink(packed, packed_cap, offsets, out_bits, err));
 }
 
 extern "C" int dega_hip_decode_packed_host(dega_hip_ctx *ctx, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits, size_t C, size_t T,
@@ -2213,19 +2186,12 @@ static int lzmh_encode_share(dega_hip_ctx *ctx, const uint8_t *in, size_t stride
   const size_t cap = dega_hip_lzmh_worst_case_bytes(stride);
   const ChunkPlan plan = lzmh_plan(C, stride, cap);
   const bool in_pinned = is_pinned(in), out_pinned = is_pinned(packed);
-  struct Ch
-  {
-    size_t c0, n;
-    int slot;
-  };
-  std::vector<Ch> chunks(plan.nchunks);
+  std::vector<Chunk> chunks(plan.nchunks);
   uint64_t running = 0;
   bool out_full = false;
   auto stage1 = [&](size_t k) -> int {
-    Ch &ch = chunks[k];
-    ch.c0 = k * plan.chunk_channels;
-    ch.n = std::min(plan.chunk_channels, C - ch.c0);
-    ch.slot = (int)(k % (size_t)plan.nslots);
+    Chunk &ch = chunks[k];
+    ch.place(plan, C, k);
     Slot &sl = pl->slot[ch.slot];
     int r;
     if ((r = slot_stream(ctx, sl)) != DEGA_OK)
@@ -2247,7 +2213,7 @@ static int lzmh_encode_share(dega_hip_ctx *ctx, const uint8_t *in, size_t stride
     return DEGA_OK;
   };
   auto stage2 = [&](size_t k) -> int {
-    Ch &ch = chunks[k];
+    const Chunk &ch = chunks[k];
     Slot &sl = pl->slot[ch.slot];
     MetaView hm(sl.hmeta.p, ch.n), dm(sl.meta.p, ch.n);
     HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
@@ -2271,17 +2237,8 @@ static int lzmh_encode_share(dega_hip_ctx *ctx, const uint8_t *in, size_t stride
     HIP_TRY(ctx, rows_to_host(pl, sl.s, packed + base, (size_t)tot, sl.c.p, (size_t)tot, 1, out_pinned), DEGA_ERROR_LIBRARY_CALL);
     return DEGA_OK;
   };
-  for (size_t k = 0; k < plan.nchunks + (size_t)plan.nslots; k++)
-  {
-    if (k >= (size_t)plan.nslots && (ret = stage2(k - (size_t)plan.nslots)) != DEGA_OK)
-      return ret;
-    if (k < plan.nchunks && (ret = stage1(k)) != DEGA_OK)
-      return ret;
-  }
-  HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
-  for (int s = 0; s < plan.nslots; s++)
-    if (pl->slot[s].s != nullptr)
-      HIP_TRY(ctx, hipStreamSynchronize(pl->slot[s].s), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = run_chunks(plan.nchunks, (size_t)plan.nslots, stage1, stage2)) != DEGA_OK || (ret = finish_slots(ctx, pl, plan.nslots)) != DEGA_OK)
+    return ret;
   offsets[C] = running;
   *total_out = running;
   if (out_full)
@@ -2302,17 +2259,10 @@ static int lzmh_decode_share(dega_hip_ctx *ctx, const uint8_t *packed, const uin
     longest_all = std::max<uint64_t>(longest_all, offsets[c + 1] - offsets[c]);
   const ChunkPlan plan = lzmh_plan(C, stride, (size_t)longest_all + 32);
   const bool in_pinned = is_pinned(packed), out_pinned = is_pinned(out);
-  struct Ch
-  {
-    size_t c0, n;
-    int slot;
-  };
-  std::vector<Ch> chunks(plan.nchunks);
+  std::vector<Chunk> chunks(plan.nchunks);
   auto stage1 = [&](size_t k) -> int {
-    Ch &ch = chunks[k];
-    ch.c0 = k * plan.chunk_channels;
-    ch.n = std::min(plan.chunk_channels, C - ch.c0);
-    ch.slot = (int)(k % (size_t)plan.nslots);
+    Chunk &ch = chunks[k];
+    ch.place(plan, C, k);
     Slot &sl = pl->slot[ch.slot];
     int r;
     if ((r = slot_stream(ctx, sl)) != DEGA_OK)
@@ -2347,7 +2297,7 @@ static int lzmh_decode_share(dega_hip_ctx *ctx, const uint8_t *packed, const uin
     return DEGA_OK;
   };
   auto stage2 = [&](size_t k) -> int {
-    Ch &ch = chunks[k];
+    const Chunk &ch = chunks[k];
     Slot &sl = pl->slot[ch.slot];
     HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
     HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
@@ -2359,14 +2309,17 @@ static int lzmh_decode_share(dega_hip_ctx *ctx, const uint8_t *packed, const uin
     }
     return DEGA_OK;
   };
-  for (size_t k = 0; k < plan.nchunks + (size_t)plan.nslots; k++)
-  {
-    if (k >= (size_t)plan.nslots && (ret = stage2(k - (size_t)plan.nslots)) != DEGA_OK)
-      return ret;
-    if (k < plan.nchunks && (ret = stage1(k)) != DEGA_OK)
-      return ret;
-  }
-  return DEGA_OK;
+  return run_chunks(plan.nchunks, (size_t)plan.nslots, stage1, stage2);
+}
+
+// contiguous channel ranges [c_g, c_g+1) for the G members of an LZMH call, cut at whole 256-channel workgroups
+static std::vector<size_t> lzmh_split_channels(size_t C, size_t G)
+{
+  std::vector<size_t> cut(G + 1, 0);
+  for (size_t g = 1; g < G; g++)
+    cut[g] = (C / G * g + std::min(C % G, g)) / 256 * 256;
+  cut[G] = C;
+  return cut;
 }
 
 static int lzmh_check(dega_hip_group *grp, size_t stride, bool encode)
@@ -2400,32 +2353,23 @@ extern "C" int dega_hip_group_lzmh_encode(dega_hip_group *grp, const uint8_t *in
     return ret == DEGA_OK ? DEGA_OK : group_fail(grp, ret, grp->ctx[0], 0);
   }
   // every device codes its range of channels into a buffer of its own; the host puts them behind one another
-  std::vector<size_t> cut(G + 1, 0);
-  for (size_t g = 1; g < G; g++)
-    cut[g] = (C / G * g + std::min(C % G, g)) / 256 * 256;
-  cut[G] = C;
+  const std::vector<size_t> cut = lzmh_split_channels(C, G);
   std::vector<std::vector<uint8_t>> tmp(G);
   std::vector<std::vector<uint64_t>> rel(G);
   std::vector<uint64_t> tot(G, 0);
-  std::vector<int> rets(G, DEGA_OK);
-  std::vector<std::thread> th;
-  for (size_t g = 0; g < G; g++)
-    th.emplace_back([&, g] {
-      const size_t n = cut[g + 1] - cut[g];
-      uint64_t text = 0;
-      for (size_t i = 0; i < n; i++)
-        text += in_len[cut[g] + i];
-      tmp[g].resize((size_t)(text + text / 4 + 64 * n + 64)); // a stream is at most 10 bits per byte of text
-      rel[g].assign(n + 1, 0);
-      rets[g] = n == 0 ? DEGA_OK
-                       : lzmh_encode_share(grp->ctx[g], in + cut[g] * stride, stride, in_len + cut[g], n, tmp[g].data(), tmp[g].size(), rel[g].data(),
-                                           out_bits + cut[g], err + cut[g], &tot[g]);
-    });
-  for (std::thread &t : th)
-    t.join();
-  for (size_t g = 0; g < G; g++)
-    if (rets[g] != DEGA_OK)
-      return group_fail(grp, rets[g], grp->ctx[g], g);
+  ret = on_members(grp, G, [&](size_t g) -> int {
+    const size_t n = cut[g + 1] - cut[g];
+    uint64_t text = 0;
+    for (size_t i = 0; i < n; i++)
+      text += in_len[cut[g] + i];
+    tmp[g].resize((size_t)(text + text / 4 + 64 * n + 64)); // a stream is at most 10 bits per byte of text
+    rel[g].assign(n + 1, 0);
+    return n == 0 ? DEGA_OK
+                  : lzmh_encode_share(grp->ctx[g], in + cut[g] * stride, stride, in_len + cut[g], n, tmp[g].data(), tmp[g].size(), rel[g].data(),
+                                      out_bits + cut[g], err + cut[g], &tot[g]);
+  });
+  if (ret != DEGA_OK)
+    return ret;
   uint64_t base = 0;
   for (size_t g = 0; g < G; g++)
   {
@@ -2462,28 +2406,10 @@ extern "C" int dega_hip_group_lzmh_decode(dega_hip_group *grp, const uint8_t *pa
       return DEGA_ERROR_INVALID_VALUE;
     }
   const size_t G = std::max<size_t>(1, std::min<size_t>(grp->ctx.size(), (C + 255) / 256));
-  std::vector<size_t> cut(G + 1, 0);
-  for (size_t g = 1; g < G; g++)
-    cut[g] = (C / G * g + std::min(C % G, g)) / 256 * 256;
-  cut[G] = C;
-  std::vector<int> rets(G, DEGA_OK);
-  auto work = [&](size_t g) {
+  const std::vector<size_t> cut = lzmh_split_channels(C, G);
+  return on_members(grp, G, [&](size_t g) -> int {
     const size_t n = cut[g + 1] - cut[g];
-    if (n != 0)
-      rets[g] = lzmh_decode_share(grp->ctx[g], packed, offsets + cut[g], in_bits + cut[g], n, out + cut[g] * stride, stride, out_len + cut[g], err + cut[g]);
-  };
-  if (G == 1)
-    work(0);
-  else
-  {
-    std::vector<std::thread> th;
-    for (size_t g = 0; g < G; g++)
-      th.emplace_back(work, g);
-    for (std::thread &t : th)
-      t.join();
-  }
-  for (size_t g = 0; g < G; g++)
-    if (rets[g] != DEGA_OK)
-      return group_fail(grp, rets[g], grp->ctx[g], g);
-  return DEGA_OK;
+    return n == 0 ? DEGA_OK
+                  : lzmh_decode_share(grp->ctx[g], packed, offsets + cut[g], in_bits + cut[g], n, out + cut[g] * stride, stride, out_len + cut[g], err + cut[g]);
+  });
 }

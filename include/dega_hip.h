@@ -213,16 +213,17 @@ size_t dega_hip_aggregate_rows(size_t T, size_t num_values); /* ceil(T / num_val
 int dega_hip_aggregate_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float *a_tc, size_t ld_out,
                            void *stream);
 int dega_hip_aggregate_host(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float *a_tc, size_t ld_out);
-/* `encode aggregate num_values=N # encode normalize # encode diff # encode seg # encode bac [adaptive]` per channel: two
-   launches on `stream`, no synchronisation -- the aggregate kernel into a scratch of T_out x ld floats that the context
-   owns, then dega_hip_encode_f32_dev over the T_out sums.  Calls on one context may use different streams like those of
+/* `encode aggregate num_values=N # encode normalize # encode diff # encode seg # encode bac [adaptive]` per channel.  It
+   IS dega_hip_encode_levels_f32_dev (below) with K = 1 and takes that call's path: two launches on `stream`, no
+   synchronisation -- the aggregate kernel into a scratch of T_out x ld floats (rounded up to four) that the context
+   owns, then the float-entry encoder over the T_out sums.  Calls on one context may use different streams like those of
    the other `dev` entry points: the scratch is shared, so a call on another stream than the previous one makes its
    stream wait (hipStreamWaitEvent; the host does not wait) until that call's encode launch has read it -- such calls
    run one after the other on the device.  The scratch only grows, by doubling; a block it has outgrown is never freed
    under a kernel that may still read it: it is kept until the context is destroyed (together less than the live block).  out / cap / out_bits / err as there; cap is
    judged against T_out (dega_hip_worst_case_bytes(T_out) always suffices), and so is the limit of 2^25 samples per
-   channel.  num_values = 1 goes straight to dega_hip_encode_f32_dev: Normalize maps both zeros to 0, the streams are
-   the same. */
+   channel.  num_values = 1 is coded straight from v_tc, without the aggregate launch: Normalize maps both zeros to 0,
+   the streams are those of dega_hip_encode_f32_dev.  num_values = 0 is refused here, with aggregate's message. */
 int dega_hip_encode_agg_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float factor, int adaptive,
                                 int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream);
 
@@ -250,9 +251,9 @@ int dega_hip_aggregate_levels_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C
 /* K x `encode aggregate num_values=N_k # encode normalize # encode diff # encode seg # encode bac [adaptive]`: the passes
    into the context's aggregate scratch (every level's sums 16-byte aligned), then K launches of the float-entry encoder
    on the same stream, level k over ceil(T / N_k) rows into out[k] / out_bits[k] / err[k] with cap[k] bytes per channel.
-   The scratch and its protocol are those of dega_hip_encode_agg_f32_dev (the event is recorded behind the last encode
-   launch).  A level with num_values 1 is coded straight from v_tc, as there.  cap[k] and the limit of 2^25 samples are
-   judged against level k's rows. */
+   The scratch and its protocol are described at dega_hip_encode_agg_f32_dev, which is this call with K = 1 (the event is
+   recorded behind the last encode launch).  A level with num_values 1 is coded straight from v_tc.  cap[k] and the limit
+   of 2^25 samples are judged against level k's rows. */
 int dega_hip_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
                                    float factor, int adaptive, int valuesize, uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits,
                                    int32_t *const *err, void *stream);
@@ -326,9 +327,13 @@ int dega_hip_encode_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const v
 int dega_hip_decode_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits,
                              void *samples, uint64_t *out_count, int32_t *err);
 /* dega_hip_encode_job_host with the aggregation of aggregate.c in front: job->samples must be DEGA_SAMPLES_F32 (anything
-   else, and num_values = 0, give DEGA_ERROR_INVALID_VALUE), job->T is the fine-grained length; every chunk of channels
-   goes up whole, is summed, coded over ceil(T / num_values) rows and packed.  The upload is num_values times what the
-   coder sees, so the link sets the time. */
+   else, and num_values = 0, give DEGA_ERROR_INVALID_VALUE with nothing written), job->T is the fine-grained length.
+   num_values = 1 is dega_hip_encode_job_host itself.  Any larger num_values is dega_hip_encode_levels_job_host (below)
+   with K = 1 and takes that call's path: every chunk of channels goes up whole, is summed, coded over
+   ceil(T / num_values) rows, packed and downloaded.  The upload is num_values times what the coder sees, so the link sets
+   the time.  `samples` must then be 4-byte aligned, as a float array is: a misaligned pointer gives
+   DEGA_ERROR_INVALID_VALUE.  A packed_cap that is too small gives DEGA_ERROR_MEMORY with the size needed in offsets[C],
+   bits and err valid, as above. */
 int dega_hip_encode_agg_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
                                  size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err);
 /* dega_hip_encode_agg_job_host for K levels: job->samples must be DEGA_SAMPLES_F32, job->T is the fine length.  Every
@@ -361,7 +366,9 @@ int dega_hip_group_encode(dega_hip_group *group, const dega_hip_job *job, const 
 int dega_hip_group_decode(dega_hip_group *group, const dega_hip_job *job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits,
                           void *samples, uint64_t *out_count, int32_t *err);
 int dega_hip_group_encode_agg(dega_hip_group *group, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
-                              size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err); /* as dega_hip_encode_agg_job_host */
+                              size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err);
+/* as dega_hip_encode_agg_job_host: num_values = 1 is dega_hip_group_encode, any larger one dega_hip_group_encode_levels
+   with K = 1, several members included (below). */
 /* as dega_hip_encode_levels_job_host.  With more than one member each of them delivers its share of each level into a
    host buffer of its own, and packed[k] is filled by host-side copies once the sizes in front are known (coarse streams
    are small).  More than one member on DISTINCT devices is unverified (tested with two members on one device). */

@@ -303,7 +303,7 @@ def test_refusals_launch_nothing(dca, ctx):
 
 # ---- host pointers: the pipeline and the groups ------------------------------------------------------------------------------------
 
-def test_encode_job_with_num_values_equals_the_device_path(dca, ctx):
+def test_encode_job_with_num_values_equals_the_device_path(dca, ctx, monkeypatch):
     import torch
     rng = np.random.default_rng(2718)
     T, Cn, N = 240, 1100, 7  # 1 100 channels: a group of two members really splits them
@@ -345,6 +345,22 @@ def test_encode_job_with_num_values_equals_the_device_path(dca, ctx):
         back, derr = ctx.decode_job(packed, offsets, hbits, T_out, adaptive=1, samples=dca.SAMPLES_F32, factor=100.0)
         ret, w = orc.decode_f32(want[17], int(b[17]), T_out, 100.0, 1)
         assert (derr == 0).all() and ret == 0 and same_floats(back[:, 17], w)
+        # several chunks on several slots, on a context and on every member (a chunk is never cut below 8 192 channels, so
+        # this takes a wider batch: three chunks on the context, two on each member of the pair)
+        Cw = 2 * 8192 + 1100
+        wv = meter(rng, 48, Cw, top=30.0)
+        out, bits, err = ctx.encode_f32(dev(wv), factor=100.0, adaptive=1, num_values=N)
+        torch.cuda.synchronize()
+        o, wb, e = out.cpu().numpy(), bits.cpu().numpy().astype(np.uint64), err.cpu().numpy()
+        assert (e == 0).all()
+        nbytes = (wb + np.uint64(7)) // np.uint64(8)
+        monkeypatch.setenv("DEGA_PIPELINE_CHUNKS", "3")
+        for who in [ctx] + groups:
+            packed, offsets, hbits, herr = who.encode_job(wv, adaptive=1, samples=dca.SAMPLES_F32, factor=100.0, num_values=N)
+            assert (herr == 0).all() and (hbits == wb).all() and (np.diff(offsets) == nbytes).all() and int(offsets[Cw]) == packed.size
+            for c in range(Cw):
+                assert packed[int(offsets[c]): int(offsets[c + 1])].tobytes() == o[c, : int(nbytes[c])].tobytes(), c
+        monkeypatch.delenv("DEGA_PIPELINE_CHUNKS")
     finally:
         for g in groups:
             g.close()
