@@ -100,6 +100,9 @@ _SIGNATURES = {
     "dega_hip_csv_write_host": (C.c_int, [_P, _P, _Z, _Z, _Z, C.c_uint, _Z, C.c_int, _P, _Z, _P, _P]),
     "dega_hip_lzmh_encode_f32_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, C.c_uint, _Z, C.c_int, _Z, _P, _Z, _P, _P, _P, _P]),
     "dega_hip_lzmh_encode_levels_f32_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _Z, C.c_uint, _Z, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "dega_hip_csv_read_dev": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, C.c_int, _P, _Z, _Z, _P, _P, _P]),
+    "dega_hip_csv_read_host": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, C.c_int, _P, _Z, _Z, _P, _P]),
+    "dega_hip_lzmh_decode_f32_dev": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, _Z, C.c_int, _P, _Z, _Z, _P, _P, _P, _P]),
     "dega_hip_profile": (C.c_int, [_P, C.c_int]),
     "dega_hip_profile_read": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int]),
 }
@@ -792,6 +795,73 @@ class Context(_JobCalls):
                                                             ptrs(bits), ptrs(text_len), ptrs(err), self._stream())
         self._check(ret, "dega_hip_lzmh_encode_levels_f32_dev")
         return list(zip(out, bits, text_len, err))
+
+    # ---- decode csv: text as float32 series, alone and behind LZMH -------------------------------------------------------
+    def csv_read(self, text, lens, max_T, column=1, separator_char=",", channels=None, ld=None, out=None):
+        """uint8 CUDA tensor [C, stride] with lens int64 [C] (what csv_write / lzmh_decode return) -> the reference's
+        `decode csv` per channel (dega_hip_csv_read_dev): (v float32 [max_T, ld], count int64 [channels], err int32
+        [channels]).  A channel with more than max_T values reports ERROR_MEMORY and the room it needs in count; one with
+        a selected field of 48 characters or more ERROR_INVALID_FORMAT.  Rows beyond a channel's count are unspecified."""
+        import torch
+        assert text.dim() == 2 and text.dtype == torch.uint8 and text.is_cuda and text.is_contiguous()
+        assert lens.dtype == torch.int64 and lens.is_cuda and lens.is_contiguous() and lens.device == text.device
+        stride = text.shape[1]
+        Cn = text.shape[0] if channels is None else int(channels)
+        assert 0 <= Cn <= text.shape[0] and lens.numel() >= Cn, "channels must be at most the rows of text"
+        ld = Cn if ld is None else int(ld)
+        max_T = int(max_T)
+        if out is None:
+            out = torch.zeros((max_T, ld), dtype=torch.float32, device=text.device)
+        assert out.dim() == 2 and out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.device == text.device
+        assert out.shape[0] >= max_T and out.shape[1] == ld, "out must be [max_T, ld]"
+        count = torch.zeros(Cn, dtype=torch.int64, device=text.device)
+        err = torch.zeros(Cn, dtype=torch.int32, device=text.device)
+        ret = library().dega_hip_csv_read_dev(self._h, text.data_ptr(), stride, lens.data_ptr(), Cn, int(column), _separator(separator_char),
+                                              out.data_ptr(), max_T, ld, count.data_ptr(), err.data_ptr(), self._stream())
+        self._check(ret, "dega_hip_csv_read_dev")
+        return out, count, err
+
+    def csv_read_host(self, text, lens, max_T, column=1, separator_char=",", channels=None, ld=None):
+        """The same for a uint8 numpy array [C, stride] in host memory (synchronous: upload, read, download):
+        (v float32 [max_T, ld], count uint64 [channels], err int32 [channels])."""
+        import numpy as np
+        assert isinstance(text, np.ndarray) and text.ndim == 2 and text.dtype == np.uint8 and text.flags.c_contiguous
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        stride = text.shape[1]
+        Cn = text.shape[0] if channels is None else int(channels)
+        assert 0 <= Cn <= text.shape[0] and lens.size >= Cn, "channels must be at most the rows of text"
+        ld = Cn if ld is None else int(ld)
+        max_T = int(max_T)
+        out = np.zeros((max_T, ld), dtype=np.float32)
+        count = np.zeros(Cn, dtype=np.uint64)
+        err = np.zeros(Cn, dtype=np.int32)
+        ret = library().dega_hip_csv_read_host(self._h, text.ctypes.data, stride, lens.ctypes.data, Cn, int(column), _separator(separator_char),
+                                               out.ctypes.data, max_T, ld, count.ctypes.data, err.ctypes.data)
+        self._check(ret, "dega_hip_csv_read_host")
+        return out, count, err
+
+    def lzmh_decode_f32(self, streams, bits, text_stride, max_T, column=1, separator_char=",", channels=None, ld=None):
+        """`decode lzmh # decode csv` per channel (dega_hip_lzmh_decode_f32_dev), the inverse of lzmh_encode_f32: streams
+        uint8 CUDA tensor [C, cap], bits int64 [C]; the text stays in a scratch of the context, text_stride bytes per
+        channel (a multiple of 16).  Returns (v float32 [max_T, ld], count int64, text_len int64, err int32); a channel
+        whose text outgrows text_stride reports ERROR_MEMORY and count 0."""
+        import torch
+        assert streams.dim() == 2 and streams.dtype == torch.uint8 and streams.is_cuda and streams.is_contiguous()
+        assert bits.dtype == torch.int64 and bits.is_cuda and bits.is_contiguous() and bits.device == streams.device
+        cap = streams.shape[1]
+        Cn = streams.shape[0] if channels is None else int(channels)
+        assert 0 <= Cn <= streams.shape[0] and bits.numel() >= Cn, "channels must be at most the rows of streams"
+        ld = Cn if ld is None else int(ld)
+        max_T = int(max_T)
+        out = torch.zeros((max_T, ld), dtype=torch.float32, device=streams.device)
+        count = torch.zeros(Cn, dtype=torch.int64, device=streams.device)
+        text_len = torch.zeros(Cn, dtype=torch.int64, device=streams.device)
+        err = torch.zeros(Cn, dtype=torch.int32, device=streams.device)
+        ret = library().dega_hip_lzmh_decode_f32_dev(self._h, streams.data_ptr(), cap, bits.data_ptr(), Cn, int(text_stride), int(column),
+                                                     _separator(separator_char), out.data_ptr(), max_T, ld, count.data_ptr(), text_len.data_ptr(),
+                                                     err.data_ptr(), self._stream())
+        self._check(ret, "dega_hip_lzmh_decode_f32_dev")
+        return out, count, text_len, err
 
     def lzmh_encode_host(self, strings, cap=None):
         """strings: list of bytes objects (one per channel).  Returns (out uint8 [C, cap], bits uint64 [C], err int32 [C])."""

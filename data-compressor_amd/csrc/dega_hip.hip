@@ -13,6 +13,7 @@
 #include "aggregate_kernels.hpp"
 #include "aggregate_levels_kernels.hpp"
 #include "csv_kernels.hpp"
+#include "csv_read_kernels.hpp"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1493,6 +1494,133 @@ extern "C" int dega_hip_lzmh_encode_levels_f32_dev(dega_hip_ctx *ctx, const floa
   return ret;
 }
 
+// ---- decode csv (DCLib/src/csv.c:13-44): text as float32 series, alone and behind LZMH ------------------------------------
+
+// The options of the stage and both layouts (everything but the pointers), for every entry point that reads.
+static int check_csv_read_options(dega_hip_ctx *ctx, size_t C, size_t column, int separator_char, size_t stride, size_t ld)
+{
+  if (column == 0 || separator_char < 0 || separator_char > 255)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: column at least 1, separator_char one byte", hipSuccess);
+  if (stride < 16 || (stride & 15u) != 0 || stride > 0x7FFFFFF0u)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: stride must be a multiple of 16 (16 .. 0x7FFFFFF0)", hipSuccess);
+  if (ld < C)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: ld < C", hipSuccess);
+  return DEGA_OK;
+}
+
+// The arguments have been checked; C is not 0.
+static int launch_csv_read(dega_hip_ctx *ctx, const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column, int separator_char,
+                           float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, int32_t *err, hipStream_t s)
+{
+  const size_t gx = (C + CSVR_BLOCK - 1) / CSVR_BLOCK;
+  if (gx > 0x7FFFFFFFu)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: too many channels for one launch", hipSuccess);
+  CsvReadArgs a;
+  a.text = text;
+  a.stride = stride;
+  a.len = len;
+  a.C = C;
+  a.column = column <= 0xFFFFFFFFu ? (uint32_t)column : 0u; // (no line has 2^32 fields: such a column selects nothing)
+  a.sep = (uint32_t)separator_char;
+  a.v = v_tc;
+  a.max_T = max_T;
+  a.ld = ld;
+  a.out_count = out_count;
+  a.err = err;
+  hipLaunchKernelGGL(dega_csv_read_kernel, dim3((unsigned)gx), dim3(CSVR_BLOCK), 0, s, a);
+  HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
+static int check_csv_read_outputs(dega_hip_ctx *ctx, const float *v_tc, size_t max_T, const uint64_t *out_count, const int32_t *err)
+{
+  if (out_count == nullptr || err == nullptr || ((uintptr_t)out_count & 7u) != 0 || ((uintptr_t)err & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: out_count and err must be arrays", hipSuccess);
+  if (max_T != 0 && (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: v_tc must be a float32 array", hipSuccess);
+  return DEGA_OK;
+}
+
+extern "C" int dega_hip_csv_read_dev(dega_hip_ctx *ctx, const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column,
+                                     int separator_char, float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, int32_t *err, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  if ((ret = check_csv_read_options(ctx, C, column, separator_char, stride, ld)) != DEGA_OK)
+    return ret;
+  if (!aligned16(text))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: text must be 16-byte aligned", hipSuccess);
+  if (C == 0)
+    return DEGA_OK;
+  if (text == nullptr || len == nullptr || ((uintptr_t)len & 7u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: text and len must be device arrays", hipSuccess);
+  if ((ret = check_csv_read_outputs(ctx, v_tc, max_T, out_count, err)) != DEGA_OK)
+    return ret;
+  if (max_T != 0 && ranges_overlap(text, C * stride, v_tc, ((max_T - 1) * ld + C) * sizeof(float)))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: v_tc overlaps text", hipSuccess);
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  return launch_csv_read(ctx, text, stride, len, C, column, separator_char, v_tc, max_T, ld, out_count, err, (hipStream_t)stream);
+}
+
+// A channel whose text did not fit its row was read as the empty text: it reports the LZMH decoder's status and no value.
+__global__ void __launch_bounds__(256) dega_csv_read_status_kernel(const int32_t *lzmh_err, size_t C, int32_t *err, uint64_t *out_count)
+{
+  const size_t c = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (c < C && lzmh_err[c] != 0)
+  {
+    err[c] = lzmh_err[c];
+    out_count[c] = 0;
+  }
+}
+
+extern "C" int dega_hip_lzmh_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t text_stride,
+                                            size_t column, int separator_char, float *v_tc, size_t max_T, size_t ld, uint64_t *out_count,
+                                            uint64_t *text_len, int32_t *err, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  if ((ret = check_csv_read_options(ctx, C, column, separator_char, text_stride, ld)) != DEGA_OK)
+    return ret;
+  if (cap < 4 || (cap & 3u) != 0 || ((uintptr_t)in & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh decode: cap must be a multiple of 4, in 4-byte aligned", hipSuccess);
+  if (C == 0)
+    return DEGA_OK;
+  if (in == nullptr || in_bits == nullptr || ((uintptr_t)in_bits & 7u) != 0 || ((uintptr_t)text_len & 7u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh decode: in and in_bits must be device arrays", hipSuccess);
+  if ((ret = check_csv_read_outputs(ctx, v_tc, max_T, out_count, err)) != DEGA_OK)
+    return ret;
+  if (max_T != 0 && ranges_overlap(in, C * cap, v_tc, ((max_T - 1) * ld + C) * sizeof(float)))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh decode: v_tc overlaps in", hipSuccess);
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  hipStream_t s = (hipStream_t)stream;
+  TextScratch t;
+  if ((ret = txt_scratch_need(ctx, C, text_stride, t)) != DEGA_OK)
+    return ret;
+  if (ctx->txt_done == nullptr)
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txt_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
+  // the text scratch may still be in use by an earlier call on another stream: this stream goes on behind it
+  if (ctx->txt_pending && ctx->txt_stream != s)
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->txt_done, 0), DEGA_ERROR_LIBRARY_CALL);
+  uint64_t *const len = text_len != nullptr ? text_len : t.len;
+  // (t.csv_err holds the LZMH decoder's status here)
+  ret = dega_hip_lzmh_decode_dev(ctx, in, cap, in_bits, C, t.text, text_stride, len, t.csv_err, s);
+  if (ret == DEGA_OK)
+    ret = launch_csv_read(ctx, t.text, text_stride, len, C, column, separator_char, v_tc, max_T, ld, out_count, err, s);
+  if (ret == DEGA_OK)
+  {
+    hipLaunchKernelGGL(dega_csv_read_status_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, t.csv_err, C, err, out_count);
+    if (hipGetLastError() != hipSuccess)
+      ret = fail(ctx, DEGA_ERROR_LIBRARY_CALL, "hipLaunchKernel", hipSuccess);
+  }
+  // (recorded whatever the launches said: the decoder may be on the stream and writes the scratch)
+  HIP_TRY(ctx, hipEventRecord(ctx->txt_done, s), DEGA_ERROR_LIBRARY_CALL);
+  ctx->txt_stream = s;
+  ctx->txt_pending = true;
+  return ret;
+}
+
 // ---- host-pointer entry points: the pipeline and the multi-device group ------------------------------------------------------
 #include "dega_pipeline.hpp"
 
@@ -1545,6 +1673,68 @@ extern "C" int dega_hip_csv_write_host(dega_hip_ctx *ctx, const float *v_tc, siz
       return ret;
     HIP_TRY(ctx, rows_to_host(pl, sl.s, out + c0 * stride, stride, sl.a.p, stride, n, out_pinned), DEGA_ERROR_LIBRARY_CALL);
     HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(out_len + c0), n * sizeof(uint64_t), d_len, n * sizeof(uint64_t), 1, len_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(err + c0), n * sizeof(int32_t), d_err, n * sizeof(int32_t), 1, err_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
+// Text rows in host memory -> float32 rows in host memory, synchronous, as plain as dega_hip_csv_write_host: chunks of
+// channels through the context's first slot (upload, one launch, download), as many channels at a time as keep the text
+// and its values under a gigabyte
+extern "C" int dega_hip_csv_read_host(dega_hip_ctx *ctx, const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column,
+                                      int separator_char, float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, int32_t *err)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  if ((ret = check_csv_read_options(ctx, C, column, separator_char, stride, ld)) != DEGA_OK)
+    return ret;
+  if (C == 0)
+    return DEGA_OK;
+  if (text == nullptr || len == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: text and len must be arrays", hipSuccess);
+  if ((ret = check_csv_read_outputs(ctx, v_tc, max_T, out_count, err)) != DEGA_OK)
+    return ret;
+  for (size_t c = 0; c < C; c++)
+    if (len[c] > stride)
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: a len[c] is larger than stride", hipSuccess);
+  Pipeline *pl;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = pipeline_get(ctx, &pl)) != DEGA_OK)
+    return ret;
+  Slot &sl = pl->slot[0];
+  if ((ret = slot_stream(ctx, sl)) != DEGA_OK)
+    return ret;
+  // a text of `stride` bytes holds at most `stride` values: more room than that is never used, and sizes stay far from wrapping
+  const size_t rows = std::min(max_T, stride);
+  const size_t per_channel = rows * sizeof(float) + stride;
+  size_t step = std::max<size_t>(1, ((size_t)1 << 30) / per_channel);
+  if (step >= 4)
+    step = step / 4 * 4;
+  const bool in_pinned = is_pinned(text), len_pinned = is_pinned(len), out_pinned = is_pinned(v_tc), count_pinned = is_pinned(out_count),
+             err_pinned = is_pinned(err);
+  for (size_t c0 = 0; c0 < C; c0 += step)
+  {
+    const size_t n = std::min(step, C - c0);
+    HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, sl.a.need(n * stride + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.c.need(n * rows * sizeof(float) + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.meta.need(n * (2 * sizeof(uint64_t) + sizeof(int32_t)) + 64), DEGA_ERROR_MEMORY);
+    uint64_t *const d_len = (uint64_t *)sl.meta.p;
+    uint64_t *const d_count = d_len + n;
+    int32_t *const d_err = (int32_t *)(d_count + n);
+    HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.a.p, text + c0 * stride, stride, stride, n, in_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_device(pl, sl.s, d_len, (const uint8_t *)(len + c0), n * sizeof(uint64_t), n * sizeof(uint64_t), 1, len_pinned),
+            DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipMemsetAsync(sl.c.p, 0, n * rows * sizeof(float) + 64, sl.s), DEGA_ERROR_LIBRARY_CALL); // (rows beyond a channel's count come back as +0.0f)
+    if ((ret = launch_csv_read(ctx, (const uint8_t *)sl.a.p, stride, d_len, n, column, separator_char, (float *)sl.c.p, rows, n, d_count, d_err,
+                               sl.s)) != DEGA_OK)
+      return ret;
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(v_tc + c0), ld * sizeof(float), sl.c.p, n * sizeof(float), rows, out_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(out_count + c0), n * sizeof(uint64_t), d_count, n * sizeof(uint64_t), 1, count_pinned),
+            DEGA_ERROR_LIBRARY_CALL);
     HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(err + c0), n * sizeof(int32_t), d_err, n * sizeof(int32_t), 1, err_pinned), DEGA_ERROR_LIBRARY_CALL);
     HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
   }

@@ -15,9 +15,12 @@
  *   dega_hip_aggregate_levels_* / dega_hip_*encode_levels*   the same stage for several num_values at once, as the
  *                       granularity study runs it: K runs of `encode aggregate num_values=N_k` over the same readings,
  *                       the base series read (and uploaded) once.
- *   dega_hip_csv_* / dega_hip_lzmh_encode*_f32_*     WriteCSV (DCLib/src/csv.c:46-65, table row DCLib/src/enc_dec.c:55; the
- *                       writer only -- ReadCSV is not replaced), alone or between `aggregate` and LZMH: the chain
- *                       `encode aggregate # encode csv # encode lzmh` of the granularity study's second codec.
+ *   dega_hip_csv_write_* / dega_hip_lzmh_encode*_f32_*     WriteCSV (DCLib/src/csv.c:46-65, table row DCLib/src/enc_dec.c:55),
+ *                       alone or between `aggregate` and LZMH: the chain `encode aggregate # encode csv # encode lzmh` of
+ *                       the granularity study's second codec.
+ *   dega_hip_csv_read_* / dega_hip_lzmh_decode_f32_*       ReadCSV (DCLib/src/csv.c:13-44, the same table row), alone or behind
+ *                       LZMH: `decode csv`, the first stage of both of the study's chains, and `decode lzmh # decode csv`,
+ *                       the inverse of its second.
  *   the bit format       DCIOLib/src/bit_file_buffer.c:220-248, 297-308 (MSB-first bits, big-endian values).
  * The reference-side binding (a row in encoders_decoders[], DCLib/src/enc_dec.c:51-60, whose enc_dec_function_t
  * (DCLib/inc/enc_dec.h:11) pulls the stream out of in_bit_buf, calls these, and pushes the result into out_bit_buf)
@@ -279,7 +282,7 @@ int dega_hip_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t 
    overlapping v_tc.  C = 0 or T = 0: nothing is launched, DEGA_OK, lengths 0.
    The environment variable DEGA_CSV_STORE=8|64 (a measurement and test knob) picks how the kernel stores its text --
    8-byte stores straight from a register, or 64-byte blocks staged in LDS; the bytes are the same.
-   There is no `decode csv` here (ReadCSV is strtof on arbitrary text: another problem). */
+   `decode csv` is dega_hip_csv_read_* below. */
 size_t dega_hip_csv_line_max(unsigned decimals, size_t column);
 size_t dega_hip_csv_worst_case_bytes(size_t T, unsigned decimals, size_t column);
 int dega_hip_csv_write_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column, int separator_char,
@@ -313,6 +316,52 @@ int dega_hip_lzmh_encode_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C,
 int dega_hip_lzmh_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
                                         unsigned decimals, size_t column, int separator_char, const size_t *text_stride, uint8_t *const *out,
                                         const size_t *cap, uint64_t *const *out_bits, uint64_t *const *text_len, int32_t *const *err, void *stream);
+
+/* ---- decode csv: text as a float32 series (ReadCSV, DCLib/src/csv.c:13-44) ------------------------------------------------ */
+/* text: uint8 [C][stride] with len[c] bytes of channel c at text + c * stride (the layout dega_hip_csv_write_dev and
+   dega_hip_lzmh_decode_dev produce; text 16-byte aligned, stride a multiple of 16, 16 .. 0x7FFFFFF0) -> v_tc: float32
+   [max_T][ld], channel c in column c, and out_count[c] values of it: the floats the reference writes for that text, in
+   order, with identical bit patterns -- signs of zero, NaN signs and payloads, subnormals and infinities included.
+   Splitting is csv.c:20-42 as it stands: a field ends at separator_char, at '\n' or at the last byte of the text; only
+   fields of column `column` are converted and '\n' resets the column to 1; a line with fewer fields yields no value, an
+   empty selected field +0.0f; and the last byte of the text is appended to a selected field whatever it is (csv.c:25-26).
+   Conversion is what glibc's strtof returns for the field in the C locale (csv.c:32): leading white space, a sign, then
+   the longest valid prefix of a decimal number (an exponent counts only with a digit in it), a hexadecimal one (0x, p
+   exponent; glibc's handling of the bit behind the 24th in subnormal hexadecimal results included), inf / infinity, nan,
+   nan(n-char-sequence) with glibc's payload (0x7fc00000 | strtoull(sequence, 0) & 0x3fffff when the whole sequence is a
+   number); no conversion gives +0.0f even behind a '-'; overflow gives an infinity, underflow a correctly rounded
+   subnormal or zero.  Rounding is to nearest, ties to even, on the exact decimal value of all the field's digits.
+   Integer arithmetic only.  One limit of the reference is NOT reproduced: its field buffer has 48 bytes (csv.c:11,18), so
+   it overruns on a selected field of 48 or more characters (the appended last byte counts, the terminator does not); such
+   a channel gets err[c] = DEGA_ERROR_INVALID_FORMAT, out_count[c] = the values in front of that field, and stops there;
+   its neighbours are unaffected.  So the longest line `encode csv` can write (47 characters + '\n') is readable
+   everywhere except as the very last line of a text, where the newline is appended to it.
+   The number of values depends on the data.  A channel with more than max_T values keeps counting without storing: it gets
+   DEGA_ERROR_MEMORY and out_count[c] = the room it needs (the convention of dega_hip_decode_var_*: call again with more
+   room).  max_T = 0 is legal and counts only (v_tc may be NULL then).  Rows at or beyond out_count[c] in column c are
+   unspecified; columns C .. ld - 1 are not written.
+   Refused with DEGA_ERROR_INVALID_VALUE before anything is launched: a null context, column 0, separator_char outside
+   0 .. 255, ld < C, a misaligned text / stride / len / out_count / err / v_tc, null arrays, v_tc overlapping text, and --
+   where the host can see it, in the host form -- a len[c] above stride (the device form gives such a channel
+   DEGA_ERROR_INVALID_VALUE and no value).  C = 0: nothing is launched, DEGA_OK.  No synchronisation. */
+int dega_hip_csv_read_dev(dega_hip_ctx *ctx, const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column, int separator_char,
+                          float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, int32_t *err, void *stream);
+/* The same from and to host memory, synchronous: chunks of channels are uploaded, read and downloaded (as
+   dega_hip_csv_write_host; no pipeline, no group).  Rows beyond a channel's count come back as +0.0f.  The call does not
+   know the counts beforehand: it holds and downloads min(max_T, stride) rows for every channel (a text of `stride` bytes
+   has no more values than that; rows of v_tc beyond them are not written), so max_T is best taken from a counting call
+   (max_T = 0) or from what wrote the text. */
+int dega_hip_csv_read_host(dega_hip_ctx *ctx, const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column, int separator_char,
+                           float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, int32_t *err);
+/* `decode lzmh # decode csv` per channel on `stream`, no synchronisation: the inverse of dega_hip_lzmh_encode_f32_dev.
+   dega_hip_lzmh_decode_dev, left as it is, writes into the context's text scratch (text_stride bytes per channel, a
+   multiple of 16; its protocol and its event are those of dega_hip_lzmh_encode_f32_dev), the reader runs over that text,
+   and a third, tiny launch merges the two statuses: a channel whose text outgrew text_stride reports DEGA_ERROR_MEMORY
+   and out_count 0, not a parse of half a text.  in / cap / in_bits as dega_hip_lzmh_decode_dev; text_len (may be NULL)
+   receives each channel's text bytes; v_tc / max_T / ld / out_count / err as dega_hip_csv_read_dev. */
+int dega_hip_lzmh_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t text_stride, size_t column,
+                                 int separator_char, float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, uint64_t *text_len, int32_t *err,
+                                 void *stream);
 
 /* ---- host pointers: the pipelined path DCCLI's stage loop (DCCLI/src/cli.c:430-466) ends up on ---------------------------- */
 /* `samples` and the outputs are HOST memory (pageable or pinned).  The batch is cut into chunks of channels, each on a
