@@ -103,6 +103,11 @@ _SIGNATURES = {
     "dega_hip_csv_read_dev": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, C.c_int, _P, _Z, _Z, _P, _P, _P]),
     "dega_hip_csv_read_host": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, C.c_int, _P, _Z, _Z, _P, _P]),
     "dega_hip_lzmh_decode_f32_dev": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, _Z, C.c_int, _P, _Z, _Z, _P, _P, _P, _P]),
+    "dega_hip_aggregate_levels_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _P, _Z, _P, _P, _P, _P, _P]),
+    "dega_hip_encode_f32_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_float, C.c_int, C.c_int, _P, _Z, _P, _P, _P]),
+    "dega_hip_encode_levels_f32_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _P, _Z, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "dega_hip_csv_write_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_uint, _Z, C.c_int, _P, _Z, _P, _P, _P]),
+    "dega_hip_lzmh_encode_levels_f32_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _P, _Z, C.c_uint, _Z, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dega_hip_profile": (C.c_int, [_P, C.c_int]),
     "dega_hip_profile_read": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int]),
 }
@@ -178,6 +183,14 @@ def _level_array(levels):
     levels = [int(n) for n in levels]
     assert all(n >= 0 for n in levels), "num_values cannot be negative"
     return levels, (_Z * max(1, len(levels)))(*levels)
+
+
+def _count_ptr(count, Cn, device):
+    """count: int64 CUDA tensor of at least Cn entries (what csv_read, lzmh_decode_f32 and decode_f32(var=True) return)"""
+    import torch
+    assert count.dtype == torch.int64 and count.is_cuda and count.is_contiguous() and count.device == device and count.numel() >= Cn, \
+        "count must be a contiguous int64 CUDA tensor with one entry per channel"
+    return count.data_ptr()
 
 
 def aggregate_levels_plan(C_, T, levels, wide=True):
@@ -498,12 +511,16 @@ class Context(_JobCalls):
         self._check(ret, "dega_hip_decode_dev")
         return x_tc, err
 
-    def aggregate(self, v_tc, num_values, out=None, channels=None):
+    def aggregate(self, v_tc, num_values, out=None, channels=None, count=None):
         """float32 CUDA tensor [T, ld] -> [ceil(T / num_values), ld_out]: every num_values consecutive readings of a channel
         summed from left to right in float32, bit for bit what the reference's `encode aggregate` writes
         (dega_hip_aggregate_dev).  channels = the first `channels` columns (default all, as encode_job).  `out` (optional)
-        is a float32 CUDA tensor of that many rows and at least `channels` columns; columns beyond are left alone."""
+        is a float32 CUDA tensor of that many rows and at least `channels` columns; columns beyond are left alone.
+        count (int64 CUDA tensor, one per channel): a ragged batch, see aggregate_levels; returns (sums, counts, err)."""
         import torch
+        if count is not None:
+            sums, counts, err = self.aggregate_levels(v_tc, [num_values], channels=channels, out=None if out is None else [out], count=count)
+            return sums[0], counts[0], err
         assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
         T, ld = v_tc.shape
         Cn = ld if channels is None else int(channels)
@@ -517,10 +534,15 @@ class Context(_JobCalls):
         self._check(ret, "dega_hip_aggregate_dev")
         return out[:T_out]
 
-    def aggregate_levels(self, v_tc, levels, channels=None, out=None):
+    def aggregate_levels(self, v_tc, levels, channels=None, out=None, count=None):
         """aggregate(v_tc, N) for every N of `levels` from one pass over v_tc where the plan allows it
         (dega_hip_aggregate_levels_dev): a list of float32 CUDA tensors [ceil(T / N), channels], in the order given, each
-        bit for bit what aggregate() gives alone.  `out` (optional): one float32 CUDA tensor per level, as in aggregate()."""
+        bit for bit what aggregate() gives alone.  `out` (optional): one float32 CUDA tensor per level, as in aggregate().
+        count (int64 CUDA tensor, one per channel; what csv_read / lzmh_decode_f32 / decode_f32(var=True) return): a ragged
+        batch (dega_hip_aggregate_levels_var_dev) -- channel c is its first count[c] rows, the rows behind them influence
+        nothing.  Returns (sums, counts, err): counts[k] int64 [channels] = ceil(count / N_k), the rows of level k's
+        column c that hold its sums (rows beyond are unspecified); err int32 [channels], ERROR_INVALID_VALUE where
+        count[c] > T."""
         import torch
         assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
         levels, nv = _level_array(levels)
@@ -535,15 +557,25 @@ class Context(_JobCalls):
         for o, r in zip(out, rows):
             assert o.dim() == 2 and o.dtype == torch.float32 and o.is_cuda and o.is_contiguous() and o.device == v_tc.device
             assert o.shape[0] >= r and o.shape[1] >= Cn, "every out must hold ceil(T / num_values) rows of at least `channels` columns"
+        if count is not None:
+            counts = [torch.zeros(Cn, dtype=torch.int64, device=v_tc.device) for _ in range(K)]
+            err = torch.zeros(Cn, dtype=torch.int32, device=v_tc.device)
+            ret = library().dega_hip_aggregate_levels_var_dev(self._h, v_tc.data_ptr(), Cn, T, ld, _count_ptr(count, Cn, v_tc.device), nv, K,
+                                                              (_P * max(1, K))(*[o.data_ptr() for o in out]), (_Z * max(1, K))(*[o.shape[1] for o in out]),
+                                                              (_P * max(1, K))(*[t.data_ptr() for t in counts]), err.data_ptr(), self._stream())
+            self._check(ret, "dega_hip_aggregate_levels_var_dev")
+            return [o[:r] for o, r in zip(out, rows)], counts, err
         ret = library().dega_hip_aggregate_levels_dev(self._h, v_tc.data_ptr(), Cn, T, ld, nv, K, (_P * max(1, K))(*[o.data_ptr() for o in out]),
                                                       (_Z * max(1, K))(*[o.shape[1] for o in out]), self._stream())
         self._check(ret, "dega_hip_aggregate_levels_dev")
         return [o[:r] for o, r in zip(out, rows)]
 
-    def encode_f32_levels(self, v_tc, levels, factor=100.0, adaptive=1, valuesize=32, cap=None):
+    def encode_f32_levels(self, v_tc, levels, factor=100.0, adaptive=1, valuesize=32, cap=None, count=None):
         """encode_f32(v_tc, num_values=N) for every N of `levels` (dega_hip_encode_levels_f32_dev): the base series is read
         once per pass of the plan, then one encode launch per level on the same stream.  cap: None, or one per level.
-        Returns a list of (out, bits, err), one per level in the order given."""
+        Returns a list of (out, bits, err), one per level in the order given.
+        count (int64 CUDA tensor, one per channel): a ragged batch (dega_hip_encode_levels_f32_var_dev); the list then
+        holds (out, bits, err, counts) with counts int64 [C] = ceil(count / N): what decode_f32 needs for that level."""
         import torch
         assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
         levels, nv = _level_array(levels)
@@ -558,6 +590,13 @@ class Context(_JobCalls):
         bits = [torch.zeros(Cn, dtype=torch.int64, device=v_tc.device) for _ in range(K)]
         err = [torch.zeros(Cn, dtype=torch.int32, device=v_tc.device) for _ in range(K)]
         ptrs = lambda ts: (_P * max(1, K))(*[t.data_ptr() for t in ts])  # noqa: E731
+        if count is not None:
+            counts = [torch.zeros(Cn, dtype=torch.int64, device=v_tc.device) for _ in range(K)]
+            ret = library().dega_hip_encode_levels_f32_var_dev(self._h, v_tc.data_ptr(), Cn, T, Cn, _count_ptr(count, Cn, v_tc.device), nv, K, float(factor),
+                                                               int(adaptive), int(valuesize), ptrs(out), (_Z * max(1, K))(*cap), ptrs(bits), ptrs(counts),
+                                                               ptrs(err), self._stream())
+            self._check(ret, "dega_hip_encode_levels_f32_var_dev")
+            return list(zip(out, bits, err, counts))
         ret = library().dega_hip_encode_levels_f32_dev(self._h, v_tc.data_ptr(), Cn, T, Cn, nv, K, float(factor), int(adaptive), int(valuesize),
                                                        ptrs(out), (_Z * max(1, K))(*cap), ptrs(bits), ptrs(err), self._stream())
         self._check(ret, "dega_hip_encode_levels_f32_dev")
@@ -579,13 +618,28 @@ class Context(_JobCalls):
         self._check(ret, "dega_hip_aggregate_host")
         return out[:T_out]
 
-    def encode_f32(self, v_tc, factor=100.0, adaptive=1, cap=None, valuesize=32, num_values=1):
+    def encode_f32(self, v_tc, factor=100.0, adaptive=1, cap=None, valuesize=32, num_values=1, count=None):
         """float32 CUDA tensor [T, C] -> streams: Normalize fused into the encode kernel (one launch).
         num_values != 1: the readings are summed in groups of num_values first (dega_hip_encode_agg_f32_dev: the aggregate
-        kernel, then the same encode over ceil(T / num_values) rows, on the same stream)."""
+        kernel, then the same encode over ceil(T / num_values) rows, on the same stream).
+        count (int64 CUDA tensor, one per channel): a ragged batch -- channel c is coded from its first count[c] rows
+        (dega_hip_encode_f32_var_dev; with num_values != 1 encode_f32_levels(count=...) with one level).  Returns
+        (out, bits, err, counts), counts = the values coded per channel: what decode_f32 needs."""
         import torch
         T, Cn = v_tc.shape
         assert v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
+        if count is not None:
+            if num_values != 1:
+                return self.encode_f32_levels(v_tc, [num_values], factor, adaptive, valuesize, None if cap is None else [cap], count=count)[0]
+            if cap is None:
+                cap = worst_case_bytes(T) if valuesize <= 32 else library().dega_hip_worst_case_bytes64(T)
+            out = torch.zeros((Cn, cap), dtype=torch.uint8, device=v_tc.device)
+            bits = torch.zeros(Cn, dtype=torch.int64, device=v_tc.device)
+            err = torch.zeros(Cn, dtype=torch.int32, device=v_tc.device)
+            ret = library().dega_hip_encode_f32_var_dev(self._h, v_tc.data_ptr(), Cn, T, Cn, _count_ptr(count, Cn, v_tc.device), float(factor), int(adaptive),
+                                                        int(valuesize), out.data_ptr(), cap, bits.data_ptr(), err.data_ptr(), self._stream())
+            self._check(ret, "dega_hip_encode_f32_var_dev")
+            return out, bits, err, count
         if num_values != 1:
             num_values = int(num_values)
             T_out = library().dega_hip_aggregate_rows(T, num_values)
@@ -608,11 +662,18 @@ class Context(_JobCalls):
         self._check(ret, "dega_hip_encode_f32_dev")
         return out, bits, err
 
-    def decode_f32(self, streams, bits, T, factor=100.0, adaptive=1, valuesize=32):
+    def decode_f32(self, streams, bits, T, factor=100.0, adaptive=1, valuesize=32, var=False):
+        """var=True: up to T values per channel; returns (v, counts int64 [C], err) -- what the count= keywords take"""
         import torch
         Cn, cap = streams.shape
         v = torch.zeros((T, Cn), dtype=torch.float32, device=streams.device)
         err = torch.zeros(Cn, dtype=torch.int32, device=streams.device)
+        if var:
+            counts = torch.zeros(Cn, dtype=torch.int64, device=streams.device)
+            ret = library().dega_hip_decode_f32_dev(self._h, streams.data_ptr(), cap, bits.data_ptr(), Cn, T, Cn, float(factor), int(adaptive),
+                                                    int(valuesize), v.data_ptr(), counts.data_ptr(), err.data_ptr(), self._stream())
+            self._check(ret, "dega_hip_decode_f32_dev")
+            return v, counts, err
         ret = library().dega_hip_decode_f32_dev(self._h, streams.data_ptr(), cap, bits.data_ptr(), Cn, T, Cn, float(factor), int(adaptive), int(valuesize),
                                                 v.data_ptr(), None, err.data_ptr(), self._stream())
         self._check(ret, "dega_hip_decode_f32_dev")
@@ -706,10 +767,12 @@ class Context(_JobCalls):
         return out, lens, err
 
     # ---- encode csv: float32 series as text, alone and in front of LZMH ------------------------------------------------
-    def csv_write(self, v_tc, decimals=2, column=1, separator_char=",", stride=None, channels=None, out=None):
+    def csv_write(self, v_tc, decimals=2, column=1, separator_char=",", stride=None, channels=None, out=None, count=None):
         """float32 CUDA tensor [T, ld] -> the reference's `encode csv` text per channel (dega_hip_csv_write_dev):
         (text uint8 [channels, stride], lens int64 [channels], err int32 [channels]).  stride (a multiple of 16) defaults
-        to csv_worst_case_bytes; a channel whose text + 16 bytes does not fit it reports ERROR_MEMORY and length 0."""
+        to csv_worst_case_bytes; a channel whose text + 16 bytes does not fit it reports ERROR_MEMORY and length 0.
+        count (int64 CUDA tensor, one per channel): a ragged batch (dega_hip_csv_write_var_dev) -- channel c's text is its
+        first count[c] readings; count[c] > T reports ERROR_INVALID_VALUE and length 0."""
         import torch
         assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
         T, ld = v_tc.shape
@@ -724,6 +787,11 @@ class Context(_JobCalls):
         assert out.shape[0] >= Cn and out.shape[1] == stride, "out must be [channels, stride]"
         lens = torch.zeros(Cn, dtype=torch.int64, device=v_tc.device)
         err = torch.zeros(Cn, dtype=torch.int32, device=v_tc.device)
+        if count is not None:
+            ret = library().dega_hip_csv_write_var_dev(self._h, v_tc.data_ptr(), Cn, T, ld, _count_ptr(count, Cn, v_tc.device), int(decimals), int(column),
+                                                       _separator(separator_char), out.data_ptr(), stride, lens.data_ptr(), err.data_ptr(), self._stream())
+            self._check(ret, "dega_hip_csv_write_var_dev")
+            return out[:Cn], lens, err
         ret = library().dega_hip_csv_write_dev(self._h, v_tc.data_ptr(), Cn, T, ld, int(decimals), int(column), _separator(separator_char),
                                                out.data_ptr(), stride, lens.data_ptr(), err.data_ptr(), self._stream())
         self._check(ret, "dega_hip_csv_write_dev")
@@ -769,11 +837,13 @@ class Context(_JobCalls):
         self._check(ret, "dega_hip_lzmh_encode_f32_dev")
         return out, bits, text_len, err
 
-    def lzmh_encode_levels_f32(self, v_tc, levels, text_stride, decimals=2, column=1, separator_char=",", cap=None, channels=None):
+    def lzmh_encode_levels_f32(self, v_tc, levels, text_stride, decimals=2, column=1, separator_char=",", cap=None, channels=None, count=None):
         """`encode aggregate num_values=N # encode csv # encode lzmh` for every N of `levels` (dega_hip_lzmh_encode_levels_f32_dev):
         the base series is read once per pass of the plan, then render + LZMH encode per level on the same stream.
         text_stride: one per level (or one for all); cap: None, or one per level.
-        Returns a list of (out, bits, text_len, err), one per level in the order given."""
+        Returns a list of (out, bits, text_len, err), one per level in the order given.
+        count (int64 CUDA tensor, one per channel): a ragged batch (dega_hip_lzmh_encode_levels_f32_var_dev); the list then
+        holds (out, bits, text_len, err, counts), counts int64 [channels] = ceil(count / N)."""
         import torch
         assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
         levels, nv = _level_array(levels)
@@ -790,6 +860,14 @@ class Context(_JobCalls):
         text_len = [torch.zeros(Cn, dtype=torch.int64, device=v_tc.device) for _ in range(K)]
         err = [torch.zeros(Cn, dtype=torch.int32, device=v_tc.device) for _ in range(K)]
         ptrs = lambda ts: (_P * max(1, K))(*[t.data_ptr() for t in ts])  # noqa: E731
+        if count is not None:
+            counts = [torch.zeros(Cn, dtype=torch.int64, device=v_tc.device) for _ in range(K)]
+            ret = library().dega_hip_lzmh_encode_levels_f32_var_dev(self._h, v_tc.data_ptr(), Cn, T, ld, _count_ptr(count, Cn, v_tc.device), nv, K,
+                                                                    int(decimals), int(column), _separator(separator_char), (_Z * max(1, K))(*strides),
+                                                                    ptrs(out), (_Z * max(1, K))(*cap), ptrs(bits), ptrs(text_len), ptrs(counts), ptrs(err),
+                                                                    self._stream())
+            self._check(ret, "dega_hip_lzmh_encode_levels_f32_var_dev")
+            return list(zip(out, bits, text_len, err, counts))
         ret = library().dega_hip_lzmh_encode_levels_f32_dev(self._h, v_tc.data_ptr(), Cn, T, ld, nv, K, int(decimals), int(column),
                                                             _separator(separator_char), (_Z * max(1, K))(*strides), ptrs(out), (_Z * max(1, K))(*cap),
                                                             ptrs(bits), ptrs(text_len), ptrs(err), self._stream())

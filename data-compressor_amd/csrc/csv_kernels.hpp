@@ -43,6 +43,7 @@ constexpr uint32_t CSV_SLACK = 16;         // room a row keeps behind its text: 
 constexpr uint32_t CSV_MAX_DECIMALS = 6;   // num_decimal_places, DCLib/src/enc_dec.c:69
 constexpr uint32_t CSV_STAGE_WORDS = 8;    // CsvStore64: 8-byte words staged per lane before they are stored (64 bytes)
 constexpr int32_t CSV_OK = 0, CSV_ERR_MEMORY = -6; // DEGA_OK, DEGA_ERROR_MEMORY
+constexpr int32_t CSV_ERR_INVALID_VALUE = -1;      // DEGA_ERROR_INVALID_VALUE
 
 struct CsvArgs
 {
@@ -55,6 +56,7 @@ struct CsvArgs
   size_t stride;         // a multiple of 16, at most 0x7FFFFFF0
   uint64_t *out_len;     // [C]
   int32_t *err;          // [C]
+  const uint64_t *count = nullptr; // the counted variant (VAR): channel c is rows 0 .. count[c] - 1 of its column
 };
 
 DG_DEV uint32_t csv_div10(uint32_t n) // exact for every 32-bit n
@@ -163,7 +165,10 @@ struct CsvWriter
 constexpr uint32_t CSV_POW10[CSV_MAX_DECIMALS + 1] = {1u, 10u, 100u, 1000u, 10000u, 100000u, 1000000u};
 
 // V: CsvStore8 or CsvStore64.
-template <typename V>
+// VAR: a ragged batch.  A lane's text ends with its own count[c]-th reading; rows are fetched up to the largest count of
+// the wave, and what lies at or beyond a lane's count (NaN, infinities, anything) is formatted like any row -- the lanes
+// stay in step -- but never written nor counted against the row's room.  count[c] > T: CSV_ERR_INVALID_VALUE, no text.
+template <typename V, bool VAR = false>
 __global__ void __launch_bounds__(256) dega_csv_kernel(const CsvArgs a)
 {
   // rows on their way: [half][row][lane], a wave's row is 64 consecutive dwords (what one LDS-DMA load fills)
@@ -187,6 +192,16 @@ __global__ void __launch_bounds__(256) dega_csv_kernel(const CsvArgs a)
   w.acc = 0;
   w.nacc = 0;
   bool ok = live;
+  // the lane's end and the wave's: both a.T in the uniform form (T_end is a constant copy of it there)
+  uint32_t mine = 0;
+  bool over = false;
+  if constexpr (VAR)
+  {
+    const uint64_t n = live ? a.count[c] : 0u;
+    over = n > a.T;
+    mine = over ? 0u : (uint32_t)n; // (the host refuses T >= 2^32 in the counted form)
+  }
+  const size_t T_end = VAR ? (size_t)wave_uniform(wave_max_u32(mine)) : a.T;
 
   auto fetch = [&](size_t t0, uint32_t half) { // rows t0 .. t0 + CSV_DEPTH - 1 (clamped to the series) into `half`
     wait_lds(); // what was read out of this half is out of it
@@ -198,17 +213,18 @@ __global__ void __launch_bounds__(256) dega_csv_kernel(const CsvArgs a)
     }
   };
 
-  if (a.T != 0)
+  if (T_end != 0)
     fetch(0, 0);
   uint32_t half = 0;
-  for (size_t t0 = 0; t0 < a.T; t0 += CSV_DEPTH, half ^= 1u)
+  for (size_t t0 = 0; t0 < T_end; t0 += CSV_DEPTH, half ^= 1u)
   {
     wait_vector_memory(); // this batch has landed (asked for one batch ago)
-    if (t0 + CSV_DEPTH < a.T)
+    if (t0 + CSV_DEPTH < T_end)
       fetch(t0 + CSV_DEPTH, half ^ 1u);
-    const uint32_t n_rows = a.T - t0 < CSV_DEPTH ? (uint32_t)(a.T - t0) : CSV_DEPTH;
+    const uint32_t n_rows = T_end - t0 < CSV_DEPTH ? (uint32_t)(T_end - t0) : CSV_DEPTH;
     for (uint32_t u = 0; u < n_rows; u++)
     {
+      const bool has = VAR ? (uint32_t)t0 + u < mine : true; // the row is one of this lane's readings
       const uint32_t bits = peer_load(rows + (half * CSV_DEPTH + u) * CSV_BLOCK + threadIdx.x);
       const uint32_t sign = bits >> 31, E = (bits >> 23) & 0xFFu, M = bits & 0x7FFFFFu;
       const uint32_t m = E != 0 ? M | 0x800000u : M; // the value is m x 2^e
@@ -282,9 +298,9 @@ __global__ void __launch_bounds__(256) dega_csv_kernel(const CsvArgs a)
 
       // ---- does the line fit?  (length() + CSV_SLACK <= stride holds before every line) ----
       const uint32_t line = a.nsep + sign + int_len + 8u * top + this_tail;
-      if (ok && line > stride - CSV_SLACK - w.length())
+      if (ok && has && line > stride - CSV_SLACK - w.length())
         ok = false;
-      if (ok)
+      if (ok && has)
       {
         for (uint32_t k = 0; k < sep_words; k++)
           w.put(sep8, 8);
@@ -307,8 +323,8 @@ __global__ void __launch_bounds__(256) dega_csv_kernel(const CsvArgs a)
       *reinterpret_cast<uint64_t *>(w.store.dst + w.store.pos) = w.acc;
     len = (uint64_t)w.store.pos + w.nacc;
   }
-  a.out_len[c] = len;
-  a.err[c] = ok ? CSV_OK : CSV_ERR_MEMORY;
+  a.out_len[c] = VAR && over ? 0u : len;
+  a.err[c] = VAR && over ? CSV_ERR_INVALID_VALUE : (ok ? CSV_OK : CSV_ERR_MEMORY);
 }
 
 } // namespace dg

@@ -12,6 +12,7 @@
 #include "lzmh_kernels.hpp"
 #include "aggregate_kernels.hpp"
 #include "aggregate_levels_kernels.hpp"
+#include "aggregate_var_kernels.hpp"
 #include "csv_kernels.hpp"
 #include "csv_read_kernels.hpp"
 
@@ -334,11 +335,13 @@ static void encode_launch(size_t C, hipStream_t s, const EncodeArgs &a)
 
 // `batch_C`: the channel count the workgroup shape is chosen by (the whole batch's when this launch is one chunk of it)
 static int launch_encode(dega_hip_ctx *ctx, const void *x, const Shape &j, size_t batch_C, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err,
-                         hipStream_t s, uint32_t *seg_state = nullptr, uint32_t seg_flags = 0)
+                         hipStream_t s, uint32_t *seg_state = nullptr, uint32_t seg_flags = 0, const uint64_t *count = nullptr)
 {
   int ret;
   if ((ret = check_job_shape(ctx, j, cap)) != DEGA_OK)
     return ret;
+  if (count != nullptr && (j.samples != DEGA_SAMPLES_F32 || seg_state != nullptr || ((uintptr_t)count & 7u) != 0))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode: counts go with float32 samples only, never with a segment state, and are 8-byte aligned", hipSuccess);
   if (j.C == 0)
     return DEGA_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
@@ -358,6 +361,7 @@ static int launch_encode(dega_hip_ctx *ctx, const void *x, const Shape &j, size_
   a.factor = j.factor;
   a.seg_state = seg_state;
   a.seg_flags = seg_flags;
+  a.count = count;
   // the bounds of normalize.c:21, rounded to float by the host compiler exactly as the reference's are
   a.lo = -(float)((uint64_t)1 << (vs - 1));
   a.hi = (float)(((uint64_t)1 << (vs - 1)) - 1);
@@ -365,7 +369,21 @@ static int launch_encode(dega_hip_ctx *ctx, const void *x, const Shape &j, size_
   (void)batch_C; // (one workgroup shape for every batch size)
   {
     LaunchTimer lt(ctx, 0, s);
-    if (vs > 32) // 64-bit values
+    if (count != nullptr) // a ragged batch: the float entry at the standard shape, and its two 64-bit forms
+    {
+      const dim3 grid((unsigned)((j.C + ENC_CHANNELS - 1) / ENC_CHANNELS));
+      const int sel = vs > 32 ? (ad ? 5 : 4) : (ad ? 2 : 0) | (vs < 32 ? 1 : 0);
+      switch (sel)
+      {
+        case 0: hipLaunchKernelGGL((dega_encode_kernel<false, false, ENC_ROWS, ENC_RING, ENC_RAW, ENC_ORING, false, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
+        case 1: hipLaunchKernelGGL((dega_encode_kernel<false, true, ENC_ROWS, ENC_RING, ENC_RAW, ENC_ORING, false, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((dega_encode_kernel<true, false, ENC_ROWS, ENC_RING, ENC_RAW, ENC_ORING, false, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
+        case 3: hipLaunchKernelGGL((dega_encode_kernel<true, true, ENC_ROWS, ENC_RING, ENC_RAW, ENC_ORING, false, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
+        case 4: hipLaunchKernelGGL((dega_encode_kernel<false, false, 4, 32, 16, 32, true, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
+        default: hipLaunchKernelGGL((dega_encode_kernel<true, false, 4, 32, 16, 32, true, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
+      }
+    }
+    else if (vs > 32) // 64-bit values
     {
       const dim3 grid((unsigned)((j.C + ENC_CHANNELS - 1) / ENC_CHANNELS));
       if (f32)
@@ -548,6 +566,17 @@ extern "C" int dega_hip_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in, siz
                                        float factor, int adaptive, int valuesize, float *v_tc, uint64_t *out_count, int32_t *err, void *stream)
 {
   return launch_decode(ctx, in, cap, in_bits, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor), C, v_tc, out_count, err, (hipStream_t)stream);
+}
+
+extern "C" int dega_hip_encode_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, float factor,
+                                           int adaptive, int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (count == nullptr && C != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode: count must be a device array of C entries", hipSuccess);
+  return launch_encode(ctx, v_tc, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor), C, out, cap, out_bits, err, (hipStream_t)stream, nullptr, 0,
+                       count);
 }
 
 static dim3 rowsplit_grid(size_t C, size_t T)
@@ -1005,6 +1034,214 @@ extern "C" int dega_hip_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_
   return ret;
 }
 
+// ---- ragged batches: a count per channel (aggregate_var_kernels.hpp) ----------------------------------------------------------
+
+template <uint32_t K>
+static void launch_var_pass(const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, size_t step, bool wide, const size_t *N,
+                            float *const *a_tc, const size_t *ld_out, uint64_t *const *out_count, int32_t *err, hipStream_t s)
+{
+  AggregateVarArgs<K> a;
+  a.v = v_tc;
+  a.C = C;
+  a.T = T;
+  a.ld = ld;
+  a.step = step;
+  a.count = count;
+  a.err = err;
+  for (uint32_t l = 0; l < K; l++)
+  {
+    a.a[l] = a_tc[l];
+    a.ld_out[l] = ld_out[l];
+    a.N[l] = (uint32_t)std::min(N[l], std::max<size_t>(T, 1));
+    a.wide_out[l] = (wide && ld_out[l] % 4 == 0 && ((uintptr_t)a_tc[l] & 15u) == 0) ? 1u : 0u;
+    a.out_count[l] = out_count[l];
+  }
+  const dim3 grid((unsigned)agg_gx(C, wide), (unsigned)std::max<size_t>(1, (T + step - 1) / step));
+  if (wide)
+    hipLaunchKernelGGL((dega_aggregate_var_kernel<AggF4, K>), grid, dim3(AGG_BLOCK), 0, s, a);
+  else
+    hipLaunchKernelGGL((dega_aggregate_var_kernel<float, K>), grid, dim3(AGG_BLOCK), 0, s, a);
+}
+
+// what the counted entry points add to their uniform twins' refusals
+static int check_counts(dega_hip_ctx *ctx, size_t C, size_t T, const uint64_t *count, uint64_t *const *out_count, size_t K, const int32_t *err)
+{
+  if (C == 0)
+    return DEGA_OK;
+  if (count == nullptr || ((uintptr_t)count & 7u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "counts: count must be a device array of C 64-bit entries, 8-byte aligned", hipSuccess);
+  if (err == nullptr || ((uintptr_t)err & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "counts: err must be a device array of C entries", hipSuccess);
+  if (K != 0 && out_count == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "counts: out_count is an array of K entries", hipSuccess);
+  for (size_t k = 0; k < K; k++)
+    if (out_count[k] == nullptr || ((uintptr_t)out_count[k] & 7u) != 0)
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "counts: every out_count[k] must be a device array of C 64-bit entries, 8-byte aligned", hipSuccess);
+  if (T > 0xFFFFFFFFu)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "counts: at most 2^32 - 1 rows", hipSuccess);
+  return DEGA_OK;
+}
+
+// The passes of the plan (planned on T, as for the uniform call) through the counted kernel, on s.  The arguments have
+// been through check_levels_dev and check_counts; T = 0 still launches: the counts and the status are the kernel's.
+static int launch_aggregate_levels_var(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, const size_t *num_values,
+                                       size_t K, float *const *a_tc, const size_t *ld_out, uint64_t *const *out_count, int32_t *err, hipStream_t s)
+{
+  if (K == 0 || C == 0)
+    return DEGA_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  const bool wide = C % 4 == 0 && ld % 4 == 0 && ((uintptr_t)v_tc & 15u) == 0; // as launch_aggregate
+  LevelsPlan p;
+  plan_levels(C, T, num_values, K, wide, p);
+  for (int q = 0; q < p.passes; q++)
+  {
+    size_t N[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS];
+    float *a[AGG_MAX_LEVELS];
+    uint64_t *oc[AGG_MAX_LEVELS];
+    uint32_t n = 0;
+    for (size_t k = 0; k < K; k++)
+      if (p.pass_of[k] == q)
+      {
+        N[n] = num_values[k];
+        a[n] = a_tc[k];
+        ldo[n] = ld_out[k];
+        oc[n] = out_count[k];
+        n++;
+      }
+    const size_t step = std::max<size_t>(p.step_of[q], 1);
+    int32_t *const e = q == 0 ? err : nullptr; // the status is one pass's to write
+    switch (n)
+    {
+      case 1: launch_var_pass<1>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
+      case 2: launch_var_pass<2>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
+      case 3: launch_var_pass<3>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
+      case 4: launch_var_pass<4>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
+      case 5: launch_var_pass<5>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
+      case 6: launch_var_pass<6>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
+      case 7: launch_var_pass<7>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
+      default: launch_var_pass<8>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
+    }
+    HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+  }
+  return DEGA_OK;
+}
+
+extern "C" int dega_hip_aggregate_levels_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
+                                                 const size_t *num_values, size_t K, float *const *a_tc, const size_t *ld_out, uint64_t *const *out_count,
+                                                 int32_t *err, void *stream)
+{
+  int ret;
+  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, num_values, K, a_tc, ld_out)) != DEGA_OK)
+    return ret;
+  if (K == 0)
+    return DEGA_OK;
+  if ((ret = check_counts(ctx, C, T, count, out_count, K, err)) != DEGA_OK)
+    return ret;
+  return launch_aggregate_levels_var(ctx, v_tc, C, T, ld, count, num_values, K, a_tc, ld_out, out_count, err, (hipStream_t)stream);
+}
+
+// err[c] = first[c] where that is set (a count above T, found by the aggregate pass): the level's own status otherwise
+__global__ void __launch_bounds__(256) dega_first_status_kernel(const int32_t *first, size_t C, int32_t *err, uint64_t *out_bits)
+{
+  const size_t c = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (c < C && first[c] != 0)
+  {
+    err[c] = first[c];
+    out_bits[c] = 0;
+  }
+}
+
+// a level with num_values 1 is coded from the readings: its counts are the caller's, 0 where one is above T
+__global__ void __launch_bounds__(256) dega_level_counts_kernel(const uint64_t *count, size_t C, size_t T, uint64_t *out_count)
+{
+  const size_t c = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (c < C)
+    out_count[c] = count[c] > T ? 0u : count[c];
+}
+
+extern "C" int dega_hip_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
+                                                  const size_t *num_values, size_t K, float factor, int adaptive, int valuesize, uint8_t *const *out,
+                                                  const size_t *cap, uint64_t *const *out_bits, uint64_t *const *out_count, int32_t *const *err, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (check_level_list(num_values, K) != DEGA_OK)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: at most 8 levels, every num_values at least 1, none twice", hipSuccess);
+  if (K == 0)
+    return DEGA_OK;
+  if (out == nullptr || cap == nullptr || out_bits == nullptr || err == nullptr || out_count == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: out, cap, out_bits, out_count and err are arrays of K entries", hipSuccess);
+  int ret;
+  // as dega_hip_encode_levels_f32_dev: every level judged before the first launch, on the rows T allows
+  Shape j[AGG_MAX_LEVELS];
+  size_t N[AGG_MAX_LEVELS], off[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, n = 0;
+  uint64_t *oc[AGG_MAX_LEVELS];
+  for (size_t k = 0; k < K; k++)
+  {
+    j[k] = shape_of(C, dega_hip_aggregate_rows(T, num_values[k]), ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor);
+    if ((ret = check_job_shape(ctx, j[k], cap[k])) != DEGA_OK)
+      return ret;
+    if (C != 0 && (out[k] == nullptr || out_bits[k] == nullptr || err[k] == nullptr || ((uintptr_t)err[k] & 3u) != 0))
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: null output", hipSuccess);
+    if (num_values[k] == 1)
+      continue;
+    N[n] = num_values[k];
+    off[n] = floats;
+    ldo[n] = ld;
+    oc[n] = out_count[k];
+    floats += round4(j[k].T * ld);
+    n++;
+  }
+  if (C == 0)
+    return DEGA_OK;
+  if ((ret = check_counts(ctx, C, T, count, out_count, K, err[0])) != DEGA_OK)
+    return ret;
+  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: v_tc must be a float32 device array", hipSuccess);
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  // the summed levels' common status (a count above T) in front of their sums
+  const size_t head = round4(C);
+  if ((ret = agg_scratch_need(ctx, head + std::max<size_t>(floats, 4))) != DEGA_OK)
+    return ret;
+  int32_t *const first = (int32_t *)ctx->agg_scratch;
+  float *a[AGG_MAX_LEVELS];
+  for (size_t i = 0; i < n; i++)
+    a[i] = ctx->agg_scratch + head + off[i];
+  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, N, n, a, ldo)) != DEGA_OK)
+    return ret;
+  hipStream_t s = (hipStream_t)stream;
+  if (ctx->agg_done == nullptr)
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->agg_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
+  if (ctx->agg_pending && ctx->agg_stream != s)
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->agg_done, 0), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = launch_aggregate_levels_var(ctx, v_tc, C, T, ld, count, N, n, a, ldo, oc, first, s)) == DEGA_OK)
+  {
+    size_t i = 0;
+    for (size_t k = 0; k < K && ret == DEGA_OK; k++)
+    {
+      if (num_values[k] == 1) // coded from v_tc with `count` itself
+      {
+        hipLaunchKernelGGL(dega_level_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, count, C, T, out_count[k]);
+        ret = launch_encode(ctx, v_tc, j[k], C, out[k], cap[k], out_bits[k], err[k], s, nullptr, 0, count);
+        continue;
+      }
+      // (a channel whose count is above T has level counts of 0: it is coded as empty, and the status launch names it)
+      ret = launch_encode(ctx, a[i++], j[k], C, out[k], cap[k], out_bits[k], err[k], s, nullptr, 0, out_count[k]);
+      if (ret == DEGA_OK)
+      {
+        hipLaunchKernelGGL(dega_first_status_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, first, C, err[k], out_bits[k]);
+        if (hipGetLastError() != hipSuccess)
+          ret = fail(ctx, DEGA_ERROR_LIBRARY_CALL, "hipLaunchKernel", hipSuccess);
+      }
+    }
+  }
+  // (recorded whatever the launches said: behind the LAST launch that reads the scratch)
+  HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
+  ctx->agg_stream = s;
+  ctx->agg_pending = true;
+  return ret;
+}
+
 // exclusive prefix sum of ceil(bits/8) over channels: one block, chunked (C is at most a few million; not a hot path)
 __global__ void __launch_bounds__(1024) dega_offsets_kernel(const uint64_t *bits, size_t C, uint64_t *offsets)
 {
@@ -1229,7 +1466,7 @@ static int check_csv_options(dega_hip_ctx *ctx, size_t C, size_t ld, unsigned de
 
 // The arguments have been checked; C and T are not 0.
 static int launch_csv(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column, int separator_char,
-                      uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, hipStream_t s)
+                      uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, hipStream_t s, const uint64_t *count = nullptr)
 {
   const size_t gx = (C + CSV_BLOCK - 1) / CSV_BLOCK;
   if (gx > 0x7FFFFFFFu)
@@ -1246,7 +1483,15 @@ static int launch_csv(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, 
   a.stride = stride;
   a.out_len = out_len;
   a.err = err;
-  if (csv_wide_stores())
+  a.count = count;
+  if (count != nullptr) // a ragged batch
+  {
+    if (csv_wide_stores())
+      hipLaunchKernelGGL((dega_csv_kernel<CsvStore64, true>), dim3((unsigned)gx), dim3(CSV_BLOCK), 0, s, a);
+    else
+      hipLaunchKernelGGL((dega_csv_kernel<CsvStore8, true>), dim3((unsigned)gx), dim3(CSV_BLOCK), 0, s, a);
+  }
+  else if (csv_wide_stores())
     hipLaunchKernelGGL(dega_csv_kernel<CsvStore64>, dim3((unsigned)gx), dim3(CSV_BLOCK), 0, s, a);
   else
     hipLaunchKernelGGL(dega_csv_kernel<CsvStore8>, dim3((unsigned)gx), dim3(CSV_BLOCK), 0, s, a);
@@ -1281,6 +1526,31 @@ extern "C" int dega_hip_csv_write_dev(dega_hip_ctx *ctx, const float *v_tc, size
   if (ranges_overlap(out, C * stride, v_tc, ((T - 1) * ld + C) * sizeof(float)))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out overlaps v_tc", hipSuccess);
   return launch_csv(ctx, v_tc, C, T, ld, decimals, column, separator_char, out, stride, out_len, err, s);
+}
+
+extern "C" int dega_hip_csv_write_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, unsigned decimals,
+                                          size_t column, int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, stride)) != DEGA_OK)
+    return ret;
+  if (!aligned16(out))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out must be 16-byte aligned", hipSuccess);
+  if (C == 0)
+    return DEGA_OK;
+  if (out == nullptr || out_len == nullptr || err == nullptr || ((uintptr_t)out_len & 7u) != 0 || ((uintptr_t)err & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out, out_len and err must be device arrays", hipSuccess);
+  if ((ret = check_counts(ctx, C, T, count, nullptr, 0, err)) != DEGA_OK)
+    return ret;
+  if (T != 0 && (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: v_tc must be a float32 device array", hipSuccess);
+  if (T != 0 && ranges_overlap(out, C * stride, v_tc, ((T - 1) * ld + C) * sizeof(float)))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out overlaps v_tc", hipSuccess);
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  // (T = 0 still launches: a count above it is the kernel's to report)
+  return launch_csv(ctx, v_tc, C, T, ld, decimals, column, separator_char, out, stride, out_len, err, (hipStream_t)stream, count);
 }
 
 // A channel whose text did not fit its row was coded as the empty text: it reports the renderer's status and no stream.
@@ -1342,11 +1612,11 @@ static int check_lzmh_outputs(dega_hip_ctx *ctx, size_t C, const uint8_t *out, s
 // render + LZMH encode + status on s; the text scratch is the caller's to guard (event protocol)
 static int launch_csv_lzmh(dega_hip_ctx *ctx, const float *rows, size_t C, size_t T, size_t ld, unsigned decimals, size_t column, int separator_char,
                            const TextScratch &t, size_t text_stride, uint8_t *out, size_t cap, uint64_t *out_bits, uint64_t *text_len, int32_t *err,
-                           hipStream_t s, bool *rendered, hipEvent_t rows_read)
+                           hipStream_t s, bool *rendered, hipEvent_t rows_read, const uint64_t *count = nullptr)
 {
   uint64_t *const len = text_len != nullptr ? text_len : t.len;
   int ret;
-  if ((ret = launch_csv(ctx, rows, C, T, ld, decimals, column, separator_char, t.text, text_stride, len, t.csv_err, s)) != DEGA_OK)
+  if ((ret = launch_csv(ctx, rows, C, T, ld, decimals, column, separator_char, t.text, text_stride, len, t.csv_err, s, count)) != DEGA_OK)
     return ret;
   *rendered = true;
   if (rows_read != nullptr) // the caller's event for "`rows` may be overwritten"
@@ -1483,6 +1753,97 @@ extern "C" int dega_hip_lzmh_encode_levels_f32_dev(dega_hip_ctx *ctx, const floa
   // renderer -- their last reader; what follows it only reads the text)
   if (ret != DEGA_OK)
     HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
+  ctx->agg_stream = s;
+  ctx->agg_pending = true;
+  if (rendered)
+  {
+    HIP_TRY(ctx, hipEventRecord(ctx->txt_done, s), DEGA_ERROR_LIBRARY_CALL);
+    ctx->txt_stream = s;
+    ctx->txt_pending = true;
+  }
+  return ret;
+}
+
+extern "C" int dega_hip_lzmh_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
+                                                       const size_t *num_values, size_t K, unsigned decimals, size_t column, int separator_char,
+                                                       const size_t *text_stride, uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits,
+                                                       uint64_t *const *text_len, uint64_t *const *out_count, int32_t *const *err, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (check_level_list(num_values, K) != DEGA_OK)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: at most 8 levels, every num_values at least 1, none twice", hipSuccess);
+  if (K == 0)
+    return DEGA_OK;
+  if (text_stride == nullptr || out == nullptr || cap == nullptr || out_bits == nullptr || err == nullptr || out_count == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: text_stride, out, cap, out_bits, out_count and err are arrays of K entries", hipSuccess);
+  int ret;
+  size_t rows[AGG_MAX_LEVELS], off[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, widest = 0;
+  for (size_t k = 0; k < K; k++) // every level judged before the first launch, as in the uniform call
+  {
+    if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, text_stride[k])) != DEGA_OK)
+      return ret;
+    if ((ret = check_lzmh_outputs(ctx, C, out[k], cap[k], out_bits[k], err[k])) != DEGA_OK)
+      return ret;
+    for (size_t i = 0; i < k; i++)
+      if (ranges_overlap(out[k], C * cap[k], out[i], C * cap[i]))
+        return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: two levels' outputs overlap", hipSuccess);
+    rows[k] = dega_hip_aggregate_rows(T, num_values[k]);
+    off[k] = floats;
+    ldo[k] = ld;
+    floats += round4(rows[k] * ld);
+    widest = std::max(widest, text_stride[k]);
+  }
+  if (C == 0)
+    return DEGA_OK;
+  if ((ret = check_counts(ctx, C, T, count, out_count, K, err[0])) != DEGA_OK)
+    return ret;
+  for (size_t k = 0; k < K; k++)
+    if (((uintptr_t)err[k] & 3u) != 0 || ((uintptr_t)out_bits[k] & 7u) != 0)
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: misaligned output", hipSuccess);
+  if (T != 0 && (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: v_tc must be a float32 device array", hipSuccess);
+  for (size_t k = 0; k < K && T != 0; k++)
+    if (ranges_overlap(out[k], C * cap[k], v_tc, ((T - 1) * ld + C) * sizeof(float)))
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: an output overlaps v_tc", hipSuccess);
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t head = round4(C); // the aggregate pass's status (a count above T) in front of the sums
+  if ((ret = agg_scratch_need(ctx, head + std::max<size_t>(floats, 4))) != DEGA_OK)
+    return ret;
+  int32_t *const first = (int32_t *)ctx->agg_scratch;
+  float *a[AGG_MAX_LEVELS];
+  for (size_t k = 0; k < K; k++)
+    a[k] = ctx->agg_scratch + head + off[k];
+  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, num_values, K, a, ldo)) != DEGA_OK)
+    return ret;
+  TextScratch t;
+  if ((ret = txt_scratch_need(ctx, C, widest, t)) != DEGA_OK)
+    return ret;
+  if (ctx->agg_done == nullptr)
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->agg_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
+  if (ctx->txt_done == nullptr)
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txt_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
+  if (ctx->agg_pending && ctx->agg_stream != s)
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->agg_done, 0), DEGA_ERROR_LIBRARY_CALL);
+  if (ctx->txt_pending && ctx->txt_stream != s)
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->txt_done, 0), DEGA_ERROR_LIBRARY_CALL);
+  bool rendered = false;
+  ret = launch_aggregate_levels_var(ctx, v_tc, C, T, ld, count, num_values, K, a, ldo, out_count, first, s);
+  for (size_t k = 0; k < K && ret == DEGA_OK; k++)
+  {
+    // every level through the aggregate stage, num_values 1 included, with that level's own counts
+    ret = launch_csv_lzmh(ctx, a[k], C, rows[k], ld, decimals, column, separator_char, t, text_stride[k], out[k], cap[k], out_bits[k],
+                          text_len != nullptr ? text_len[k] : nullptr, err[k], s, &rendered, nullptr, out_count[k]);
+    if (ret == DEGA_OK)
+    {
+      hipLaunchKernelGGL(dega_first_status_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, first, C, err[k], out_bits[k]);
+      if (hipGetLastError() != hipSuccess)
+        ret = fail(ctx, DEGA_ERROR_LIBRARY_CALL, "hipLaunchKernel", hipSuccess);
+    }
+  }
+  // (recorded whatever the launches said; the status launches read the aggregate scratch's head, so its event goes last)
+  HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
   ctx->agg_stream = s;
   ctx->agg_pending = true;
   if (rendered)

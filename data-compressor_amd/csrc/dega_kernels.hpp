@@ -91,6 +91,7 @@ struct EncodeArgs
   float factor, lo, hi;      // normalization factor; range of normalize.c:21 for the value size, rounded to float by the host compiler
   uint32_t *seg_state;       // NULL: whole channels in one launch.  Else [ENC_STATE_WORDS][C], see above
   uint32_t seg_flags;        // ENC_SEG_*
+  const uint64_t *count = nullptr; // VAR variants: [C], channel c is rows 0 .. count[c] - 1 of its column (no segments then)
 };
 
 // `symbols`: no channel of the batch codes more symbols than this (cum[0] starts at 3 and grows by one per symbol until
@@ -182,7 +183,14 @@ constexpr uint32_t ENC_PUB_DONE = 1u << 24, ENC_PUB_BAD = 1u << 25;
 // FILLS / WRITES: which of the two this wave is.  (A wave each: the coding wave of a SIMD must never wait for either, and
 // three waves get more instructions per cycle out of a SIMD than two -- one wave doing both left the coder waiting for
 // room a sixth of its time.)
-template <bool NARROW, uint32_t ROWS, uint32_t RING, uint32_t RAW, uint32_t ORING, bool W64, bool F32IN, bool FILLS, bool WRITES>
+// VAR: a ragged batch (a.count).  A lane's channel ends with its own count; the wave's row loop ends at the largest count of
+// its lanes (T_end) and takes the straight-line batch only while every lane still has ROWS rows (T_all, the smallest
+// count): both are wave uniform, computed once.  Rows at or beyond a lane's count are fetched with the others and may hold
+// anything -- they reach neither the bit queue, nor `last`, nor the range check.  The tail word and "done" stay one
+// publication per wave, after the wave's last row: a lane that ended early simply has no new word for the coder, which
+// already steps with lanes that have none.  count[c] > T: the channel is coded as empty and the writer reports
+// ERR_INVALID_VALUE and 0 bits.  Without VAR, T_end and T_all are a.T and the code is what it was.
+template <bool NARROW, uint32_t ROWS, uint32_t RING, uint32_t RAW, uint32_t ORING, bool W64, bool F32IN, bool FILLS, bool WRITES, bool VAR = false>
 DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const uint32_t *raw_col, uint32_t *oring_col, uint32_t *rows_wave, uint32_t *pub_mine,
                                 const uint32_t *pub_peer, uint32_t lane, size_t c, bool live, size_t c_wave0)
 {
@@ -220,6 +228,16 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
     wr.drained = wr.pos > 0u ? wr.pos - 1u : 0u; // everything but the held-back word is in the slab
   }
   uint32_t rrd = 0; // raw entries absorbed
+  uint32_t mine = 0; // VAR: the lane's count
+  bool over = false; // VAR: count[c] > T
+  if constexpr (VAR)
+  {
+    const uint64_t n = live ? a.count[c] : 0u;
+    over = n > a.T;
+    mine = over ? 0u : (uint32_t)n; // (T <= 2^25)
+  }
+  const size_t T_end = VAR && FILLS ? (size_t)wave_uniform(wave_max_u32(mine)) : a.T;
+  const size_t T_all = VAR && FILLS ? (size_t)wave_uniform(wave_min_u32(live ? mine : 0xFFFFFFFFu)) : a.T;
 
   // Input rows travel HBM -> LDS directly (LDS-DMA, `global_load_lds_dword`: one 256-byte row segment per wave
   // instruction, no VGPR destination) and are read from LDS by the next fill; the next batch is requested right after a
@@ -275,7 +293,9 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
 
   // ---- one batch of ROWS rows (or what is left of them) into the lanes' bit queues -------------------------------------------
   auto fill_batch = [&]() {
-    const size_t left = a.T - t;
+    const size_t left = T_end - t; // the wave's
+    // the lane's own: rows of this batch below its count
+    const size_t left_mine = VAR ? ((size_t)mine > t ? (size_t)mine - t : 0u) : left;
     if constexpr (W64)
     {
       const uint64_t vmask64 = a.valuesize >= 64u ? ~0ull : (1ull << a.valuesize) - 1ull;
@@ -283,7 +303,7 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
       {
 #pragma unroll
         for (uint32_t i = 0; i < ROWS; i++)
-          if (i < left)
+          if (i < left_mine)
           {
             uint64_t u;
             if constexpr (F32IN)
@@ -318,7 +338,7 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
         for (uint32_t i = 0; i < ROWS; i++)
         {
           int32_t n;
-          all_in_range = normalize_value(__uint_as_float(xr[i]), a.factor, n, a.lo, a.hi, vmask) && all_in_range;
+          all_in_range = (normalize_value(__uint_as_float(xr[i]), a.factor, n, a.lo, a.hi, vmask) || (VAR && i >= left_mine)) && all_in_range; // (VAR: the clamped row's verdict says nothing about a lane that has ended)
           xr[i] = (uint32_t)n;
         }
         if (!all_in_range && lane_err == OK)
@@ -352,7 +372,7 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
         wseen |= w[i];
       }
       const bool plain = NARROW ? false : ((seen >> 31) | (wseen >> 16)) == 0u; // narrow values: range check per sample
-      if (left >= ROWS && !wave_any(!plain && live))
+      if ((VAR ? t + ROWS <= T_all : left >= ROWS) && !wave_any(!plain && live))
       {
         // the steady state: a full batch of short codewords, straight-line appends
         if (live)
@@ -370,7 +390,7 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
 #pragma unroll
         for (uint32_t i = 0; i < ROWS; i++)
         {
-          if (i < left)
+          if (i < left_mine)
           {
             const SegWord sw = diff_seg<NARROW>(xr[i], last, vhalf);
             if (!sw.ok && lane_err == OK)
@@ -384,7 +404,7 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
   };
 
   wave_priority<(WRITES ? DG_ENC_WRITE_PRIO : DG_ENC_FILL_PRIO)>();
-  if (FILLS && a.T > 0)
+  if (FILLS && T_end > 0)
     issue_rows(0);
   bool tail_placed = !FILLS; // the final, partial word is in the ring (or stays in the state) and "done" is published
   uint32_t pub_flags = 0;
@@ -393,14 +413,18 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
     const uint32_t cp = peer_load(pub_peer);
     bool worked = false;
     // ---- fill: the same ROWS rows for every lane, as soon as every lane's ring has room for what they may add -----------
-    if (FILLS && t < a.T)
+    if (FILLS && t < T_end)
     {
       const bool room = ((q.wr - cp) & 0xFFFFu) + FILL_WORDS <= RING;
       if (wave_all(room))
       {
         wait_vector_memory();
         fill_batch();
-        if (t < a.T)
+#if defined(DEGA_SIM)
+        if constexpr (VAR)
+          (void)wave_any(false); // (the emulator's lanes are threads: all of them have read their rows before one fetches into the others' columns)
+#endif
+        if (t < T_end)
           issue_rows(t); // in flight while the coder works through this batch
         worked = true;
       }
@@ -409,7 +433,7 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
     // batch of worst-case codewords can leave the ring full to the last slot (RING words queued), and the next slot is
     // then the oldest word the coder has not taken yet.  When more rows follow in a later launch the bits stay in the
     // queue (saved with the state) and the coder gets no partial word.
-    if (FILLS && t >= a.T && !tail_placed && !wave_any(((q.wr - cp) & 0xFFFFu) >= RING))
+    if (FILLS && t >= T_end && !tail_placed && !wave_any(((q.wr - cp) & 0xFFFFu) >= RING))
     {
       uint32_t tail_bits = 0;
       if (!more)
@@ -556,6 +580,11 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
 #endif
       const bool bad_value = FILLS ? lane_err != OK : (peer_load(pub_peer) & ENC_PUB_BAD) != 0u;
       a.err[c] = bad_value ? ERR_INVALID_VALUE : wr.err;
+      if (VAR && over)
+      {
+        a.out_bits[c] = 0;
+        a.err[c] = ERR_INVALID_VALUE;
+      }
     }
   }
 }
@@ -785,7 +814,7 @@ DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const u
 constexpr uint32_t ENC_SHORT_TABLE = 8192;
 constexpr size_t ENC_SHORT_T = (ENC_SHORT_TABLE - 70) / 65; // 124
 template <bool ADAPTIVE, bool NARROW = false, uint32_t ROWS = ENC_ROWS, uint32_t RING = ENC_RING, uint32_t RAW = ENC_RAW, uint32_t ORING = ENC_ORING, bool W64 = false,
-          bool F32IN = false, uint32_t GROUPS = ENC_PAIRS, uint32_t TABW = DIV_TABLE_SIZE>
+          bool F32IN = false, uint32_t GROUPS = ENC_PAIRS, uint32_t TABW = DIV_TABLE_SIZE, bool VAR = false>
 __global__ void __launch_bounds__(GROUPS * 192) dega_encode_kernel(const EncodeArgs a)
 {
   constexpr uint32_t LDS_ROWS = (W64 && !F32IN) ? 2 * ROWS : ROWS;
@@ -830,9 +859,9 @@ __global__ void __launch_bounds__(GROUPS * 192) dega_encode_kernel(const EncodeA
   if (role == 1)
     encode_coding_wave<ADAPTIVE, RING, RAW>(a, tab, ring_col, raw_col, pub_coder, pub_filler, pub_writer, lane, c, live);
   else if (role == 0)
-    encode_helping_wave<NARROW, ROWS, RING, RAW, ORING, W64, F32IN, true, false>(a, ring_col, raw_col, oring_col, rows_wave, pub_filler, pub_coder, lane, c, live, c_wave0);
+    encode_helping_wave<NARROW, ROWS, RING, RAW, ORING, W64, F32IN, true, false, VAR>(a, ring_col, raw_col, oring_col, rows_wave, pub_filler, pub_coder, lane, c, live, c_wave0);
   else
-    encode_helping_wave<NARROW, ROWS, RING, RAW, ORING, W64, F32IN, false, true>(a, ring_col, raw_col, oring_col, rows_wave, pub_writer, pub_coder, lane, c, live, c_wave0);
+    encode_helping_wave<NARROW, ROWS, RING, RAW, ORING, W64, F32IN, false, true, VAR>(a, ring_col, raw_col, oring_col, rows_wave, pub_writer, pub_coder, lane, c, live, c_wave0);
 }
 
 // =====================================================================================================================

@@ -21,6 +21,10 @@
  *   dega_hip_csv_read_* / dega_hip_lzmh_decode_f32_*       ReadCSV (DCLib/src/csv.c:13-44, the same table row), alone or behind
  *                       LZMH: `decode csv`, the first stage of both of the study's chains, and `decode lzmh # decode csv`,
  *                       the inverse of its second.
+ *   dega_hip_*_var_dev (the block "ragged batches")         the same stages over channels of DIFFERENT lengths: what the
+ *                       readers and decoders above deliver (a float matrix and a count per channel) goes into
+ *                       aggregate, the DEGA float entry, `encode csv` and the LZMH chain as it is, every channel coded as
+ *                       the reference codes a file of that channel's own length.
  *   the bit format       DCIOLib/src/bit_file_buffer.c:220-248, 297-308 (MSB-first bits, big-endian values).
  * The reference-side binding (a row in encoders_decoders[], DCLib/src/enc_dec.c:51-60, whose enc_dec_function_t
  * (DCLib/inc/enc_dec.h:11) pulls the stream out of in_bit_buf, calls these, and pushes the result into out_bit_buf)
@@ -362,6 +366,55 @@ int dega_hip_csv_read_host(dega_hip_ctx *ctx, const uint8_t *text, size_t stride
 int dega_hip_lzmh_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t text_stride, size_t column,
                                  int separator_char, float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, uint64_t *text_len, int32_t *err,
                                  void *stream);
+
+/* ---- ragged batches: a count per channel through aggregate, encode and csv, device pointers -------------------------------- */
+/* Meter files differ in length (gaps, start dates, new meters), and dega_hip_csv_read_dev, dega_hip_lzmh_decode_f32_dev and
+   the decoders' out_count report it: a matrix [max_T][ld] and a count per channel.  These entry points take exactly that.
+   count: device uint64 [C], 8-byte aligned.  Channel c is rows 0 .. count[c] - 1 of column c of v_tc [T][ld]; T is the
+   number of rows the matrix has (the reader's max_T).  Rows t >= count[c] of column c may be LOADED but influence no
+   output and no status, whatever they hold (NaN, infinities, values outside Normalize's range: the readers leave them
+   unspecified).  Every channel's result is bit for bit what the uniform twin gives for that channel alone with
+   T = count[c] -- what the reference's chain gives on count[c] floats; padding a short channel instead would change the
+   last sum of every level and the stream.  count[c] = 0 is the reference's result on an empty input: `aggregate` writes
+   nothing, `... # encode bac adaptive` gives the 3 bits 0x20 (`... # encode bac`: what dega_hip_encode_f32_dev gives for
+   T = 0), `encode csv # encode lzmh` 0 bits.  count[c] > T gives that channel DEGA_ERROR_INVALID_VALUE, no output and
+   output counts / lengths / bits of 0; its neighbours are unaffected.  Host-side refusals, alignment rules, the scratch
+   buffers with their event protocol and the stream semantics are the uniform twin's; in addition a null or misaligned
+   count / out_count[k] and T >= 2^32 are refused, and C != 0 with T = 0 still launches (the counts decide).  A count
+   never goes together with a segment state (there is no counted dega_hip_encode_segment_dev).
+   Cost: a wave walks rows up to the largest count among its 64 channels.  The aggregate's loop is the uniform kernel's
+   while every lane of the wave still has rows and selects per lane behind that; the coder's filling wave takes its
+   straight-line batch only while every lane still has a full batch of rows, and the general per-row writer from the
+   wave's shortest channel on.  Sorting channels by length is the caller's business. */
+/* K = 1 .. DEGA_AGG_MAX_LEVELS levels; one level is this call with K = 1.  Level k receives rows 0 .. out_count[k][c] - 1 of
+   column c of a_tc[k], out_count[k][c] = ceil(count[c] / num_values[k]) (out_count[k]: device uint64 [C]); rows beyond
+   are not promised (they are left as they were).  a_tc[k] needs the rows T allows, dega_hip_aggregate_rows(T,
+   num_values[k]).  Passes are planned by dega_hip_aggregate_levels_plan on T, as for dega_hip_aggregate_levels_dev; every
+   pass, single-level ones included, runs the counted kernel.  err: device int32 [C]. */
+int dega_hip_aggregate_levels_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
+                                      const size_t *num_values, size_t K, float *const *a_tc, const size_t *ld_out, uint64_t *const *out_count,
+                                      int32_t *err, void *stream);
+/* dega_hip_encode_f32_dev over a ragged batch: valuesize 1 .. 64; cap and the limit of 2^25 samples are judged against T. */
+int dega_hip_encode_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, float factor, int adaptive,
+                                int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream);
+/* dega_hip_encode_levels_f32_dev over a ragged batch: dega_hip_aggregate_levels_var_dev into the aggregate scratch, then the
+   counted encoder per level with that level's counts.  out_count[k] is required: it is the intermediate, and what the
+   caller needs to decode level k (dega_hip_decode_f32_dev with out_count).  A level with num_values 1 is coded from v_tc
+   with `count` itself (out_count[k] receives it, 0 where it is above T).  cap[k] is judged against the rows T allows for level k. */
+int dega_hip_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
+                                       const size_t *num_values, size_t K, float factor, int adaptive, int valuesize, uint8_t *const *out,
+                                       const size_t *cap, uint64_t *const *out_bits, uint64_t *const *out_count, int32_t *const *err, void *stream);
+/* dega_hip_csv_write_dev over a ragged batch: channel c's text is its first count[c] readings. */
+int dega_hip_csv_write_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, unsigned decimals,
+                               size_t column, int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, void *stream);
+/* dega_hip_lzmh_encode_levels_f32_dev over a ragged batch -- the chain WITH `aggregate` in it, as its twin: every level,
+   num_values 1 included, through the counted aggregate kernel, then per level the counted renderer, the LZMH encoder and the
+   status launches.  out_count[k] is required (level k's values per channel: what dega_hip_lzmh_decode_f32_dev reports
+   back); text_len may be NULL, and so may any text_len[k]. */
+int dega_hip_lzmh_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
+                                            const size_t *num_values, size_t K, unsigned decimals, size_t column, int separator_char,
+                                            const size_t *text_stride, uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits,
+                                            uint64_t *const *text_len, uint64_t *const *out_count, int32_t *const *err, void *stream);
 
 /* ---- host pointers: the pipelined path DCCLI's stage loop (DCCLI/src/cli.c:430-466) ends up on ---------------------------- */
 /* `samples` and the outputs are HOST memory (pageable or pinned).  The batch is cut into chunks of channels, each on a
