@@ -108,11 +108,14 @@ _SIGNATURES = {
     "dega_hip_encode_levels_f32_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _P, _Z, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "dega_hip_csv_write_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_uint, _Z, C.c_int, _P, _Z, _P, _P, _P]),
     "dega_hip_lzmh_encode_levels_f32_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _P, _Z, C.c_uint, _Z, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dega_hip_to_time_major_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _Z, _P, _P, _Z, _P]),
+    "dega_hip_to_channel_major_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _Z, _P, _P, _Z, _P]),
     "dega_hip_profile": (C.c_int, [_P, C.c_int]),
     "dega_hip_profile_read": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int]),
 }
 
 SAMPLES_I32, SAMPLES_BE32, SAMPLES_I64, SAMPLES_F32 = 0, 1, 2, 3
+SAMPLES_CHANNEL_MAJOR = 0x100  # DEGA_SAMPLES_CHANNEL_MAJOR: OR-ed into Job.samples by layout="channel"
 
 
 class Job(C.Structure):
@@ -211,16 +214,53 @@ def _sample_dtype(samples):
     return {SAMPLES_I32: np.dtype(np.int32), SAMPLES_BE32: np.dtype(">i4"), SAMPLES_I64: np.dtype(np.int64), SAMPLES_F32: np.dtype(np.float32)}[samples]
 
 
+def _host_layout(x, layout, samples, channels, T):
+    """The assertions of a host job's sample array (as encode_segments makes them for its tensor: dtype, C-contiguity, shape)
+    and what the job says about it: (C, T, ld, samples field).  layout "time": x is [T, ld], channels = its first `channels`
+    columns; "channel": x is [C, ld], one series per row, T = the first T values of each (default: all ld)."""
+    import numpy as np
+    assert layout in ("time", "channel"), 'layout is "time" or "channel"'
+    assert isinstance(x, np.ndarray) and x.ndim == 2 and x.flags.c_contiguous, "the samples must be a C-contiguous 2-d numpy array"
+    assert x.dtype == _sample_dtype(samples), "the array's dtype must be the sample type's: nothing is converted behind the caller's back"
+    if layout == "time":
+        assert T is None or int(T) == x.shape[0], "T is the number of rows of a time-major array"
+        Cn = x.shape[1] if channels is None else int(channels)
+        assert 0 <= Cn <= x.shape[1], "channels must be at most the row pitch"
+        return Cn, x.shape[0], x.shape[1], int(samples)
+    Cn = x.shape[0] if channels is None else int(channels)
+    Tn = x.shape[1] if T is None else int(T)
+    assert 0 <= Cn <= x.shape[0], "channels must be at most the number of rows of a channel-major array"
+    assert 0 <= Tn <= x.shape[1], "T must be at most the pitch between channels"
+    return Cn, Tn, x.shape[1], int(samples) | SAMPLES_CHANNEL_MAJOR
+
+
 class _JobCalls:
     """encode_job / decode_job on numpy arrays: the packed host-pointer surface, shared by Context (one device) and Group
     (every device).  Subclasses provide _enc_fn / _dec_fn / _handle / _check."""
 
-    def encode_job(self, x_tc, adaptive=1, valuesize=32, samples=SAMPLES_I32, factor=100.0, packed_cap=None, channels=None, packed=None, num_values=1):
+    def encode_job(self, x_tc, adaptive=1, valuesize=32, samples=SAMPLES_I32, factor=100.0, packed_cap=None, channels=None, packed=None, num_values=1,
+                   layout="time", T=None):
         """x_tc: [T, ld] array of the sample type (channels = the first `channels` columns, default all).
         Returns (packed uint8 [total], offsets uint64 [C+1], bits uint64 [C], err int32 [C]).
         num_values != 1 (float32 samples only): every num_values consecutive readings of a channel are summed on the
-        device first, as the reference's `encode aggregate` does, and the ceil(T / num_values) sums are coded."""
+        device first, as the reference's `encode aggregate` does, and the ceil(T / num_values) sums are coded.
+        layout="channel": the array is [C, ld] instead, one series per row (DEGA_SAMPLES_CHANNEL_MAJOR), T = the first T
+        values of every row (default all); it goes up as it lies and is transposed on the device.  The array must then
+        be C-contiguous and of the sample type (big-endian samples: dtype ">i4"); the results are those of the
+        time-major call on its transpose."""
         import numpy as np
+        assert layout in ("time", "channel"), 'layout is "time" or "channel"'
+        if layout == "channel":
+            Cn, Tn, _, _ = dims = _host_layout(x_tc, layout, samples, channels, T)
+            num_values = int(num_values)
+            assert num_values >= 0
+            assert packed is None or (isinstance(packed, np.ndarray) and packed.dtype == np.uint8 and packed.flags.c_contiguous and packed.ndim == 1)
+            if num_values != 1:
+                rows = library().dega_hip_aggregate_rows(Tn, num_values)
+                return self._encode_packed(self._enc_agg_fn(), (num_values,), "encode_job(num_values=%d, layout=channel)" % num_values, x_tc, rows,
+                                           adaptive, valuesize, samples, factor, packed_cap, channels, packed, dims)
+            return self._encode_packed(self._enc_fn(), (), "encode_job(layout=channel)", x_tc, Tn, adaptive, valuesize, samples, factor, packed_cap, channels,
+                                       packed, dims)
         if num_values != 1:
             # the layout the library is told is the layout the array has: nothing is converted or copied behind the caller's back
             num_values = int(num_values)
@@ -236,13 +276,17 @@ class _JobCalls:
             x_tc = np.ascontiguousarray(x_tc, dtype=_sample_dtype(samples))
         return self._encode_packed(self._enc_fn(), (), "encode_job", x_tc, x_tc.shape[0], adaptive, valuesize, samples, factor, packed_cap, channels, packed)
 
-    def _encode_packed(self, fn, lead, what, x_tc, rows, adaptive, valuesize, samples, factor, packed_cap, channels, packed):
+    def _encode_packed(self, fn, lead, what, x_tc, rows, adaptive, valuesize, samples, factor, packed_cap, channels, packed, dims=None):
         """fn(handle, job, *lead, samples, packed, packed_cap, offsets, bits, err) over x_tc as it is; `rows` values are coded
-        per channel.  A packed_cap that was too small is replaced once by the size the library reports in offsets[C]."""
+        per channel.  A packed_cap that was too small is replaced once by the size the library reports in offsets[C].
+        dims: (C, T, ld, samples field) of _host_layout where the array is not [T, ld]."""
         import numpy as np
-        T, pitch = x_tc.shape
-        Cn = pitch if channels is None else int(channels)
-        job = Job(Cn, T, pitch, int(adaptive), int(valuesize), int(samples), float(factor))
+        if dims is None:
+            T, pitch = x_tc.shape
+            Cn = pitch if channels is None else int(channels)
+            dims = (Cn, T, pitch, int(samples))
+        Cn = dims[0]
+        job = Job(dims[0], dims[1], dims[2], int(adaptive), int(valuesize), dims[3], float(factor))
         if packed_cap is None:
             packed_cap = Cn * (rows * 2 + 64)  # generous for meter data; the call says so if it is not
         offsets = np.zeros(Cn + 1, dtype=np.uint64)
@@ -258,19 +302,18 @@ class _JobCalls:
         self._check(ret, what)
         return buf[: int(offsets[Cn])], offsets, bits, err
 
-    def encode_job_levels(self, x_tc, levels, adaptive=1, valuesize=32, factor=100.0, packed_cap=None, channels=None):
+    def encode_job_levels(self, x_tc, levels, adaptive=1, valuesize=32, factor=100.0, packed_cap=None, channels=None, layout="time", T=None):
         """encode_job(..., samples=SAMPLES_F32, num_values=N) for every N of `levels` from ONE upload of x_tc (float32 numpy
         [T, ld]; dega_hip_encode_levels_job_host / dega_hip_group_encode_levels).  packed_cap: None, or one size per
-        level.  Returns a list of (packed, offsets, bits, err), one per level in the order given."""
+        level.  Returns a list of (packed, offsets, bits, err), one per level in the order given.
+        layout="channel": x_tc is float32 [C, ld], one series per row, as in encode_job."""
         import numpy as np
         assert isinstance(x_tc, np.ndarray) and x_tc.ndim == 2 and x_tc.flags.c_contiguous and x_tc.dtype == np.float32, \
-            "x_tc must be a C-contiguous float32 [T, ld] numpy array"
+            "x_tc must be a C-contiguous float32 [T, ld] (layout=\"channel\": [C, ld]) numpy array"
         levels, nv = _level_array(levels)
         K = len(levels)
-        T, pitch = x_tc.shape
-        Cn = pitch if channels is None else int(channels)
-        assert 0 <= Cn <= pitch, "channels must be at most the row pitch"
-        job = Job(Cn, T, pitch, int(adaptive), int(valuesize), SAMPLES_F32, float(factor))
+        Cn, T, pitch, field = _host_layout(x_tc, layout, SAMPLES_F32, channels, T)
+        job = Job(Cn, T, pitch, int(adaptive), int(valuesize), field, float(factor))
         rows = [library().dega_hip_aggregate_rows(T, n) for n in levels]
         caps = [Cn * (r * 2 + 64) for r in rows] if packed_cap is None else [int(c) for c in packed_cap]
         assert len(caps) == K, "one packed_cap per level"
@@ -290,16 +333,27 @@ class _JobCalls:
         self._check(ret, "encode_job_levels(%s)" % levels)
         return [(bufs[k][: int(offsets[k][Cn])], offsets[k], bits[k], err[k]) for k in range(K)]
 
-    def decode_job(self, packed, offsets, bits, T, adaptive=1, valuesize=32, samples=SAMPLES_I32, factor=100.0, var=False, out=None):
-        """The inverse.  Returns (x [T, C] of the sample type, err) or, with var=True, (x, counts, err)."""
+    def decode_job(self, packed, offsets, bits, T, adaptive=1, valuesize=32, samples=SAMPLES_I32, factor=100.0, var=False, out=None, layout="time"):
+        """The inverse.  Returns (x [T, C] of the sample type, err) or, with var=True, (x, counts, err).
+        layout="channel": x is [C, T] instead (out: a C-contiguous [>= C, ld >= T] array of the sample type, whose padding
+        is left alone; the whole array is returned); with var=True the values behind a channel's count are zero."""
         import numpy as np
+        assert layout in ("time", "channel"), 'layout is "time" or "channel"'
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         bits = np.ascontiguousarray(bits, dtype=np.uint64)
         Cn = bits.size
-        x = out if out is not None else np.zeros((T, Cn), dtype=_sample_dtype(samples))
         counts = np.zeros(Cn, dtype=np.uint64)
         err = np.zeros(Cn, dtype=np.int32)
+        if layout == "channel":
+            x = out if out is not None else np.zeros((Cn, T), dtype=_sample_dtype(samples))
+            dims = _host_layout(x, layout, samples, Cn, T)
+            job = Job(dims[0], dims[1], dims[2], int(adaptive), int(valuesize), dims[3], float(factor))
+            ret = self._dec_fn()(self._handle(), C.byref(job), packed.ctypes.data, offsets.ctypes.data, bits.ctypes.data, x.ctypes.data,
+                                 counts.ctypes.data if var else None, err.ctypes.data)
+            self._check(ret, "decode_job(layout=channel)")
+            return (x, counts, err) if var else (x, err)
+        x = out if out is not None else np.zeros((T, Cn), dtype=_sample_dtype(samples))
         job = Job(Cn, T, x.shape[1] if x.ndim == 2 else Cn, int(adaptive), int(valuesize), int(samples), float(factor))
         ret = self._dec_fn()(self._handle(), C.byref(job), packed.ctypes.data, offsets.ctypes.data, bits.ctypes.data, x.ctypes.data,
                              counts.ctypes.data if var else None, err.ctypes.data)
@@ -510,6 +564,53 @@ class Context(_JobCalls):
                                             x_tc.data_ptr(), err.data_ptr(), self._stream())
         self._check(ret, "dega_hip_decode_dev")
         return x_tc, err
+
+    @staticmethod
+    def _layout_tensor(x, what):
+        import torch
+        assert isinstance(x, torch.Tensor) and x.dim() == 2 and x.is_cuda and x.is_contiguous() and x.element_size() in (4, 8), \
+            "%s must be a contiguous 2-d CUDA tensor of 4- or 8-byte elements" % what
+
+    def to_time_major(self, x_ct, T=None, count=None, ld=None, out=None):
+        """x_ct: CUDA tensor [C, stride] of 4- or 8-byte elements, one series per row -> [T, C] with out[t, c] = x_ct[c, t]
+        (dega_hip_to_time_major_dev; one kernel on the current stream).  T: the first T values of every row (default all).
+        out (optional): a tensor [>= T, ld >= C] of the same dtype, or ld: the row pitch of a new one; columns C .. ld - 1
+        are not written.  count (int64 CUDA tensor, one per channel): out[t, c] is zero bits for t >= count[c], whatever
+        x_ct holds there.  Returns the [T, C] view of the destination."""
+        import torch
+        self._layout_tensor(x_ct, "x_ct")
+        Cn, stride = x_ct.shape
+        T = stride if T is None else int(T)
+        assert 0 <= T <= stride, "T must be at most the pitch between channels"
+        if out is None:
+            out = torch.empty((T, Cn if ld is None else int(ld)), dtype=x_ct.dtype, device=x_ct.device)
+        self._layout_tensor(out, "out")
+        assert out.dtype == x_ct.dtype and out.device == x_ct.device and (ld is None or int(ld) == out.shape[1])
+        assert out.shape[0] >= T and out.shape[1] >= Cn, "out must hold T rows of at least C columns"
+        ret = library().dega_hip_to_time_major_dev(self._h, x_ct.data_ptr(), Cn, T, stride, x_ct.element_size(),
+                                                   None if count is None else _count_ptr(count, Cn, x_ct.device), out.data_ptr(), out.shape[1], self._stream())
+        self._check(ret, "dega_hip_to_time_major_dev")
+        return out[:T, :Cn]
+
+    def to_channel_major(self, x_tc, channels=None, count=None, stride=None, out=None):
+        """The inverse: x_tc [T, ld] -> [C, T] with out[c, t] = x_tc[t, c] (dega_hip_to_channel_major_dev).  channels: the first
+        `channels` columns (default all).  out (optional): a tensor [>= C, stride >= T], or stride: the pitch of a new one;
+        values T .. stride - 1 of a row are not written.  count: out[c, t] is zero bits for t >= count[c].  Returns the
+        [C, T] view of the destination."""
+        import torch
+        self._layout_tensor(x_tc, "x_tc")
+        T, ld = x_tc.shape
+        Cn = ld if channels is None else int(channels)
+        assert 0 <= Cn <= ld, "channels must be at most the row pitch"
+        if out is None:
+            out = torch.empty((Cn, T if stride is None else int(stride)), dtype=x_tc.dtype, device=x_tc.device)
+        self._layout_tensor(out, "out")
+        assert out.dtype == x_tc.dtype and out.device == x_tc.device and (stride is None or int(stride) == out.shape[1])
+        assert out.shape[0] >= Cn and out.shape[1] >= T, "out must hold C rows of at least T values"
+        ret = library().dega_hip_to_channel_major_dev(self._h, x_tc.data_ptr(), Cn, T, ld, x_tc.element_size(),
+                                                      None if count is None else _count_ptr(count, Cn, x_tc.device), out.data_ptr(), out.shape[1], self._stream())
+        self._check(ret, "dega_hip_to_channel_major_dev")
+        return out[:Cn, :T]
 
     def aggregate(self, v_tc, num_values, out=None, channels=None, count=None):
         """float32 CUDA tensor [T, ld] -> [ceil(T / num_values), ld_out]: every num_values consecutive readings of a channel

@@ -15,6 +15,7 @@
 #include "aggregate_var_kernels.hpp"
 #include "csv_kernels.hpp"
 #include "csv_read_kernels.hpp"
+#include "transpose_kernels.hpp"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -308,6 +309,7 @@ struct Shape
   size_t C, T, ld;
   int adaptive, valuesize, samples;
   float factor;
+  bool cmajor = false; // host jobs only: the caller's array is [C][ld], ld >= T (DEGA_SAMPLES_CHANNEL_MAJOR; `samples` holds the type alone)
 };
 
 static int check_job_shape(dega_hip_ctx *ctx, const Shape &j, size_t cap)
@@ -319,7 +321,9 @@ static int check_job_shape(dega_hip_ctx *ctx, const Shape &j, size_t cap)
       ((j.samples == DEGA_SAMPLES_I32 || j.samples == DEGA_SAMPLES_BE32) && wide) || (j.samples == DEGA_SAMPLES_I64 && !wide))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "sample type and valuesize do not go together (int32 / big-endian: 1..32, int64: 33..64, float32: 1..64)",
                 hipSuccess);
-  return check_shape(ctx, j.C, j.T, j.ld, cap, 32);
+  if (j.cmajor && j.ld < j.T)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "ld < T (channel-major samples: ld is the pitch between channels)", hipSuccess);
+  return check_shape(ctx, j.C, j.T, j.cmajor ? j.C : j.ld, cap, 32);
 }
 
 template <bool AD, bool NARROW, bool F32>
@@ -687,6 +691,86 @@ extern "C" int dega_hip_aggregate_dev(dega_hip_ctx *ctx, const float *v_tc, size
                                       size_t ld_out, void *stream)
 {
   return launch_aggregate(ctx, v_tc, C, T, ld, num_values, a_tc, ld_out, (hipStream_t)stream);
+}
+
+// ---- channel-major <-> time-major ---------------------------------------------------------------------------------------
+
+template <typename E>
+static void transpose_launch(bool wide_ld, bool wide_st, dim3 grid, hipStream_t s, const TransposeArgs &a)
+{
+  constexpr uint32_t V = 16 / sizeof(E);
+  if (wide_ld && wide_st)
+    hipLaunchKernelGGL((dega_transpose_kernel<E, V, V>), grid, dim3(TR_BLOCK), 0, s, a);
+  else if (wide_ld)
+    hipLaunchKernelGGL((dega_transpose_kernel<E, V, 1>), grid, dim3(TR_BLOCK), 0, s, a);
+  else if (wide_st)
+    hipLaunchKernelGGL((dega_transpose_kernel<E, 1, V>), grid, dim3(TR_BLOCK), 0, s, a);
+  else
+    hipLaunchKernelGGL((dega_transpose_kernel<E, 1, 1>), grid, dim3(TR_BLOCK), 0, s, a);
+}
+
+// S[R][sp] -> D[K][dp], D[k][r] = S[r][k]; the channel (what `count` is indexed by) is the source row when channel_rows.
+// to time-major: R = C, K = T; to channel-major: R = T, K = C.
+static int launch_transpose(dega_hip_ctx *ctx, const void *src, size_t R, size_t K, size_t sp, size_t esz, const uint64_t *count, bool channel_rows,
+                            void *dst, size_t dp, hipStream_t s)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (esz != 4 && esz != 8)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "transpose: elem_bytes must be 4 or 8", hipSuccess);
+  if (sp < K || dp < R)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "transpose: ld < C or stride < T", hipSuccess);
+  if (R == 0 || K == 0)
+    return DEGA_OK;
+  if (src == nullptr || dst == nullptr || ((uintptr_t)src & (esz - 1)) != 0 || ((uintptr_t)dst & (esz - 1)) != 0 || ((uintptr_t)count & 7u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "transpose: the images must be aligned to their elements, the counts to 8 bytes", hipSuccess);
+  {
+    // the byte ranges of the two images; sizes whose ranges do not fit the address space are refused, not wrapped
+    size_t sn, dn;
+    uintptr_t s1, d1;
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+    if (__builtin_mul_overflow(R - 1, sp, &sn) || __builtin_add_overflow(sn, K, &sn) || __builtin_mul_overflow(sn, esz, &sn) ||
+        __builtin_add_overflow(s0, sn, &s1) || __builtin_mul_overflow(K - 1, dp, &dn) || __builtin_add_overflow(dn, R, &dn) ||
+        __builtin_mul_overflow(dn, esz, &dn) || __builtin_add_overflow(d0, dn, &d1))
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "transpose: an image does not fit the address space", hipSuccess);
+    if (d0 < s1 && s0 < d1)
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "transpose: source and destination overlap", hipSuccess);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  TransposeArgs a;
+  a.src = src;
+  a.dst = dst;
+  a.R = R;
+  a.K = K;
+  a.sp = sp;
+  a.dp = dp;
+  a.count = count;
+  a.count_on_rows = channel_rows ? 1u : 0u;
+  uint32_t gx, gy;
+  if (!tr_plan(R, K, TR_GRID_X, a, gx, gy))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "transpose: too many tiles for one launch", hipSuccess);
+  // 16-byte loads / stores on each side whose every row starts on a 16-byte boundary (a vector that crosses the edge of
+  // the logical region is done by elements in its lane, so the extents do not matter)
+  const size_t V = 16 / esz;
+  const bool wide_ld = ((uintptr_t)src & 15u) == 0 && sp % V == 0, wide_st = ((uintptr_t)dst & 15u) == 0 && dp % V == 0;
+  if (esz == 4)
+    transpose_launch<uint32_t>(wide_ld, wide_st, dim3(gx, gy), s, a);
+  else
+    transpose_launch<uint64_t>(wide_ld, wide_st, dim3(gx, gy), s, a);
+  HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
+extern "C" int dega_hip_to_time_major_dev(dega_hip_ctx *ctx, const void *x_ct, size_t C, size_t T, size_t stride, size_t elem_bytes, const uint64_t *count,
+                                          void *x_tc, size_t ld, void *stream)
+{
+  return launch_transpose(ctx, x_ct, C, T, stride, elem_bytes, count, true, x_tc, ld, (hipStream_t)stream);
+}
+
+extern "C" int dega_hip_to_channel_major_dev(dega_hip_ctx *ctx, const void *x_tc, size_t C, size_t T, size_t ld, size_t elem_bytes, const uint64_t *count,
+                                             void *x_ct, size_t stride, void *stream)
+{
+  return launch_transpose(ctx, x_tc, T, C, ld, elem_bytes, count, false, x_ct, stride, (hipStream_t)stream);
 }
 
 static int agg_scratch_need(dega_hip_ctx *ctx, size_t floats)

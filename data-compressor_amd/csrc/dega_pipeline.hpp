@@ -716,8 +716,16 @@ static bool read_in_place()
 // Phase A of one device's share: channels [0, j.C) of `samples` (host, row pitch j.ld).  Uploads, codes and sizes every
 // chunk; with `deliver` the packed bytes of each chunk also go out at once (base = running total); without, they stay
 // on the device (gathered) for encode_deliver().  bits / err / offsets (relative to this share) are final on return.
-static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, const EncodeSink &sink, bool deliver, EncodeRun &run)
+static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples, const EncodeSink &sink, bool deliver, EncodeRun &run)
 {
+  // Channel-major samples ([C][ld], ld >= T): a chunk's channels go up as they lie -- n rows of T samples, one contiguous
+  // copy when ld == T -- into the slot's SLAB buffer, which is free until the chunk's encode launch writes it (everything
+  // is on the slot's stream), and dega_transpose_kernel makes the time-major image in the samples' buffer from there.  No
+  // staging buffer of its own: the slabs hold max(cap, T * esz) bytes per channel then, and plan_chunks is told so.
+  // Whole chunks only: no bands and no in-place read of pinned memory (the kernel's filling waves read rows).
+  const bool cmajor = job.cmajor;
+  Shape j = job;
+  j.cmajor = false; // (the chunks' shapes below describe time-major images on the device)
   int ret;
   Pipeline *pl;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
@@ -725,7 +733,8 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, 
     return ret;
   const size_t esz = sample_bytes(j);
   const size_t cap = usual_cap(j);
-  const size_t dev_per_channel = std::max(j.T * esz + 64, cap) + 16 + cap + 64;
+  const size_t slab_bytes = cmajor ? std::max(cap, j.T * esz) : cap; // per channel, what the slot's slab buffer holds
+  const size_t dev_per_channel = std::max(j.T * esz + 64, cap) + 16 + slab_bytes + 64;
   const ChunkPlan plan = plan_chunks(j.C, j.T * esz, dev_per_channel, deliver ? 0 : 1);
   if (plan.nslots < 0)
     return fail(ctx, DEGA_ERROR_MEMORY, "the device's share of the batch does not fit its memory", hipSuccess);
@@ -733,7 +742,7 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, 
   run.total = 0;
   bool out_full = false;
   const bool samples_pinned = is_pinned(samples), packed_pinned = is_pinned(sink.packed);
-  const bool in_place = samples_pinned && read_in_place();
+  const bool in_place = samples_pinned && read_in_place() && !cmajor;
 
   TRACE("encode share: C %zu T %zu, %zu chunks of %zu channels, %d slots", j.C, j.T, plan.nchunks, plan.chunk_channels, plan.nslots);
   auto stage1 = [&](size_t k) -> int {
@@ -745,15 +754,15 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, 
     if ((r = slot_stream(ctx, sl)) != DEGA_OK)
       return r;
     HIP_TRY(ctx, sl.a.need(ch.n * std::max(j.T * esz + 64, cap) + 4096), DEGA_ERROR_MEMORY); // the samples, later the packed streams
-    HIP_TRY(ctx, sl.b.need(ch.n * cap + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.b.need(ch.n * slab_bytes + 64), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.meta.need(MetaView::bytes(ch.n)), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.hmeta.need(MetaView::bytes(ch.n)), DEGA_ERROR_MEMORY);
     MetaView dm(sl.meta.p, ch.n);
     Shape cj = j;
     cj.C = ch.n;
     cj.ld = ch.n;
-    const uint8_t *const src = (const uint8_t *)samples + ch.c0 * esz;
-    const size_t band_rows = band_rows_of(plan, j, ch.n * esz);
+    const uint8_t *const src = (const uint8_t *)samples + ch.c0 * (cmajor ? j.ld : 1) * esz;
+    const size_t band_rows = cmajor ? 0 : band_rows_of(plan, j, ch.n * esz);
     ch.rows = (const uint8_t *)sl.a.p;
     ch.rows_ld = ch.n;
     void *dev_src = nullptr;
@@ -775,6 +784,14 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &j, const void *samples, 
       if ((r = launch_encode(ctx, ch.rows, cj, j.C, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
         return r;
       TRACE("chunk %zu: read in place", k);
+    }
+    else if (cmajor)
+    {
+      HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.b.p, src, j.ld * esz, j.T * esz, ch.n, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
+      if ((r = launch_transpose(ctx, sl.b.p, ch.n, j.T, j.T, esz, nullptr, true, sl.a.p, ch.n, sl.s)) != DEGA_OK ||
+          (r = launch_encode(ctx, sl.a.p, cj, j.C, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
+        return r;
+      TRACE("chunk %zu: channel-major, transposed on the device", k);
     }
     else if (band_rows == 0)
     {
@@ -969,8 +986,13 @@ static size_t meta_stride(size_t n) // the K MetaViews of a slot lie one behind 
 // j: C, ld, factor, adaptive, valuesize of the job; j.T the FINE length.  Always delivers (no resident phase).
 // `sized`: set once every chunk has been coded and sized, i.e. bits / err / offsets / total of every level are complete;
 // a DEGA_ERROR_MEMORY with `sized` false is a failed allocation, one with `sized` true a packed buffer that is too small.
-static int encode_levels_share(dega_hip_ctx *ctx, const Shape &j, const size_t *num_values, size_t K, const void *samples, LevelSink *sink, bool &sized)
+static int encode_levels_share(dega_hip_ctx *ctx, const Shape &job, const size_t *num_values, size_t K, const void *samples, LevelSink *sink, bool &sized)
 {
+  // channel-major samples: as in encode_share, through the slot's slab buffer (free until the first encode launch of the
+  // chunk), which then holds max(the levels' slabs, T * esz) bytes per channel
+  const bool cmajor = job.cmajor;
+  Shape j = job;
+  j.cmajor = false;
   sized = false;
   int ret;
   Pipeline *pl;
@@ -992,7 +1014,8 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &j, const size_t *
     sink[k].full = false;
   }
   const size_t fine_bytes = std::max(j.T * esz + 64, cap_sum); // per channel: the fine rows, later every level's packed streams
-  const size_t dev_per_channel = fine_bytes + 16 + sum_rows * esz + 16 * K + cap_sum + 64 + K * 32;
+  const size_t slab_bytes = cmajor ? std::max(cap_sum, j.T * esz) : cap_sum;
+  const size_t dev_per_channel = fine_bytes + 16 + sum_rows * esz + 16 * K + slab_bytes + 64 + K * 32;
   const ChunkPlan plan = plan_chunks(j.C, j.T * esz, dev_per_channel, 0);
   struct LevelChunk : Chunk
   {
@@ -1015,11 +1038,18 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &j, const size_t *
     const size_t n = ch.n;
     HIP_TRY(ctx, sl.c.need(n * fine_bytes + 4096), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.a.need((sum_rows * n + 4 * K) * esz + 64), DEGA_ERROR_MEMORY);
-    HIP_TRY(ctx, sl.b.need(n * cap_sum + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.b.need(n * slab_bytes + 64), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.meta.need(K * meta_stride(n)), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.hmeta.need(K * meta_stride(n)), DEGA_ERROR_MEMORY);
-    const uint8_t *const src = (const uint8_t *)samples + ch.c0 * esz;
-    HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, src, j.ld * esz, n * esz, j.T, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
+    const uint8_t *const src = (const uint8_t *)samples + ch.c0 * (cmajor ? j.ld : 1) * esz;
+    if (cmajor)
+    {
+      HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.b.p, src, j.ld * esz, j.T * esz, n, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
+      if ((r = launch_transpose(ctx, sl.b.p, n, j.T, j.T, esz, nullptr, true, sl.c.p, n, sl.s)) != DEGA_OK)
+        return r;
+    }
+    else
+      HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, src, j.ld * esz, n * esz, j.T, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
     // the sums of the summed levels: the plan's passes over the chunk's image (pitch n), every level 16-byte aligned
     size_t N[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, m = 0;
     float *a[AGG_MAX_LEVELS];
@@ -1136,9 +1166,17 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &j, const size_t *
 
 // ---- decode ------------------------------------------------------------------------------------------------------------
 
-static int decode_share(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed, const uint64_t *offsets, const uint64_t *bits, void *samples,
+static int decode_share(dega_hip_ctx *ctx, const Shape &job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *bits, void *samples,
                         uint64_t *out_count, int32_t *err)
 {
+  // Channel-major samples ([C][ld], ld >= T): dega_transpose_kernel runs behind the chunk's decode kernel, from the samples'
+  // buffer into the buffer of the chunk's packed streams -- free once they have been spread into slabs, which the slot's
+  // stream has waited for -- which holds max(the streams, n * T samples) then (plan_chunks is told so).  With out_count the
+  // kernel gets the chunk's device counts, so the tail of every series goes home as zeros; the download is n rows of T
+  // samples at the caller's pitch, whose padding is not touched.  Whole chunks only: no bands.
+  const bool cmajor = job.cmajor;
+  Shape j = job;
+  j.cmajor = false;
   int ret;
   Pipeline *pl;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
@@ -1150,7 +1188,8 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed
   uint64_t longest_all = 0;
   for (size_t c = 0; c < j.C; c++)
     longest_all = std::max<uint64_t>(longest_all, offsets[c + 1] - offsets[c]);
-  const size_t dev_per_channel = j.T * osz + (size_t)(span / std::max<size_t>(j.C, 1)) + (size_t)longest_all + 64;
+  const size_t mean_stream = (size_t)(span / std::max<size_t>(j.C, 1));
+  const size_t dev_per_channel = j.T * osz + (cmajor ? std::max(mean_stream, j.T * osz) : mean_stream) + (size_t)longest_all + 64;
   // At most four chunks: a decode kernel takes its channels' serial time however few they are, the hardware queues run
   // few of them side by side, and the rows go home in bands beside the running kernel anyway (65 536 x 10 800 from
   // pinned memory: 8 chunks 83 ms, 4: 63 ms, 2: 66.5 ms, 1: 66 ms).
@@ -1180,7 +1219,7 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed
       longest = std::max<uint64_t>(longest, offsets[ch.c0 + i + 1] - offsets[ch.c0 + i]);
     const size_t cap = ((size_t)longest + 16 + 3) & ~(size_t)3; // room for the decoder's word look-ahead
     ch.cap = cap;
-    HIP_TRY(ctx, sl.a.need((size_t)nbytes + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.a.need((cmajor ? std::max<size_t>((size_t)nbytes, ch.n * j.T * osz) : (size_t)nbytes) + 64), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.b.need(ch.n * cap + 64), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.c.need(ch.n * j.T * osz + 64), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.meta.need(MetaView::bytes(ch.n)), DEGA_ERROR_MEMORY);
@@ -1230,7 +1269,7 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed
     cj.ld = ch.n;
     // few, long channels (see encode_share): the rows go home in bands while the kernel is still decoding; every wave of 64
     // channels reports the rows it has stored in a word of pinned host memory
-    ch.band_rows = out_count == nullptr ? band_rows_of(plan, j, ch.n * osz) : 0;
+    ch.band_rows = out_count == nullptr && !cmajor ? band_rows_of(plan, j, ch.n * osz) : 0;
     uint32_t *reports = nullptr;
     if (ch.band_rows != 0)
     {
@@ -1244,6 +1283,8 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed
     if ((r = launch_decode(ctx, (const uint8_t *)sl.b.p, cap, dm.bits, cj, j.C, sl.c.p, out_count != nullptr ? dm.counts : nullptr, dm.err, sl.s, reports,
                            (uint32_t)ch.band_rows)) != DEGA_OK)
       return r;
+    if (cmajor && (r = launch_transpose(ctx, sl.c.p, j.T, ch.n, ch.n, osz, out_count != nullptr ? dm.counts : nullptr, false, sl.a.p, j.T, sl.s)) != DEGA_OK)
+      return r;
     // counts and err come back right behind the kernel
     HIP_TRY(ctx, hipMemcpyAsync(hm.counts, dm.counts, ch.n * sizeof(uint64_t) + ch.n * sizeof(int32_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
     return DEGA_OK;
@@ -1252,7 +1293,9 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed
   auto stage2 = [&](size_t k) -> int {
     DecChunk &ch = chunks[k];
     Slot &sl = pl->slot[ch.slot];
-    if (ch.band_rows == 0)
+    if (cmajor)
+      HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)samples + ch.c0 * j.ld * osz, j.ld * osz, sl.a.p, j.T * osz, ch.n, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
+    else if (ch.band_rows == 0)
       HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)samples + ch.c0 * osz, j.ld * osz, sl.c.p, ch.n * osz, j.T, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
     else
     {
@@ -1421,7 +1464,10 @@ extern "C" const char *dega_hip_group_last_error(const dega_hip_group *g)
 
 static Shape shape_from_job(const dega_hip_job *job)
 {
-  return shape_of(job->C, job->T, job->ld, job->adaptive, job->valuesize, job->samples, job->factor);
+  // (any other bit above the sample types stays in `samples` and is refused with it)
+  Shape j = shape_of(job->C, job->T, job->ld, job->adaptive, job->valuesize, job->samples & ~DEGA_SAMPLES_CHANNEL_MAJOR, job->factor);
+  j.cmajor = (job->samples & DEGA_SAMPLES_CHANNEL_MAJOR) != 0;
+  return j;
 }
 
 // contiguous channel ranges [c_g, c_g+1), whole 512-channel workgroups where the batch allows
@@ -1532,7 +1578,7 @@ static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samp
     }
     free_b = std::min(free_b, f);
   }
-  const size_t per_channel = std::max(j.T * esz + 64, usual_cap(j)) + 16 + usual_cap(j) + 64 + 256;
+  const size_t per_channel = std::max(j.T * esz + 64, usual_cap(j)) + 16 + (j.cmajor ? std::max(usual_cap(j), j.T * esz) : usual_cap(j)) + 64 + 256;
   size_t round_channels = std::max<size_t>(G * 512, std::min<size_t>(j.C, free_b / 10 * 6 / per_channel * G / 512 * 512));
   uint64_t base = 0;
   bool out_full = false;
@@ -1553,7 +1599,7 @@ static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samp
         ss.offsets = rel[g].data();
         ss.bits = sink.bits + r0 + cut[g];
         ss.err = sink.err + r0 + cut[g];
-        rets[g] = encode_share(grp->ctx[g], sj, (const uint8_t *)samples + (r0 + cut[g]) * esz, ss, false, runs[g]);
+        rets[g] = encode_share(grp->ctx[g], sj, (const uint8_t *)samples + (r0 + cut[g]) * (j.cmajor ? j.ld : 1) * esz, ss, false, runs[g]);
       });
     for (std::thread &t : th)
       t.join();
@@ -1633,7 +1679,7 @@ static int decode_on_group(dega_hip_group *grp, const Shape &j, const uint8_t *p
   return on_members(grp, G, [&](size_t g) -> int {
     Shape sj = j;
     sj.C = cut[g + 1] - cut[g];
-    return decode_share(grp->ctx[g], sj, packed, offsets + cut[g], bits + cut[g], (uint8_t *)samples + cut[g] * osz,
+    return decode_share(grp->ctx[g], sj, packed, offsets + cut[g], bits + cut[g], (uint8_t *)samples + cut[g] * (j.cmajor ? j.ld : 1) * osz,
                         out_count != nullptr ? out_count + cut[g] : nullptr, err + cut[g]);
   });
 }
@@ -1690,8 +1736,9 @@ static int check_levels_job(const dega_hip_job *job, const size_t *num_values, s
   *what = "encode levels: at most 8 levels, every num_values at least 1, none twice";
   if (check_level_list(num_values, K) != DEGA_OK)
     return DEGA_ERROR_INVALID_VALUE;
-  *what = "encode levels: the job's samples must be DEGA_SAMPLES_F32, ld >= C";
-  if (job == nullptr || job->samples != DEGA_SAMPLES_F32 || job->ld < job->C)
+  *what = "encode levels: the job's samples must be DEGA_SAMPLES_F32, ld >= C (channel-major: ld >= T)";
+  if (job == nullptr || (job->samples & ~DEGA_SAMPLES_CHANNEL_MAJOR) != DEGA_SAMPLES_F32 ||
+      job->ld < ((job->samples & DEGA_SAMPLES_CHANNEL_MAJOR) != 0 ? job->T : job->C))
     return DEGA_ERROR_INVALID_VALUE;
   *what = "encode levels: packed, packed_cap, offsets, out_bits and err are arrays of K entries, samples float32 rows";
   if (K != 0 && (packed == nullptr || packed_cap == nullptr || offsets == nullptr || out_bits == nullptr || err == nullptr))
@@ -1767,7 +1814,7 @@ static int encode_levels_on_group(dega_hip_group *grp, const dega_hip_job *job, 
   ret = on_members(grp, G, [&](size_t g) -> int {
     Shape sj = j;
     sj.C = cut[g + 1] - cut[g];
-    const void *const src = (const uint8_t *)samples + cut[g] * sizeof(float);
+    const void *const src = (const uint8_t *)samples + cut[g] * (j.cmajor ? j.ld : 1) * sizeof(float);
     bool sized = false;
     int r = encode_levels_share(grp->ctx[g], sj, num_values, K, src, sinks[g].data(), sized);
     // A level that outgrew the member's buffer but fits the caller's (a chunk redone with worst-case slabs): once more,
@@ -1853,7 +1900,7 @@ static int check_agg_job(const dega_hip_job *job, size_t num_values, const void 
                          uint64_t *out_bits, int32_t *err, const char **what)
 {
   *what = "encode_agg: num_values must be at least 1 and the job's samples DEGA_SAMPLES_F32";
-  if (job == nullptr || num_values == 0 || job->samples != DEGA_SAMPLES_F32 || offsets == nullptr)
+  if (job == nullptr || num_values == 0 || (job->samples & ~DEGA_SAMPLES_CHANNEL_MAJOR) != DEGA_SAMPLES_F32 || offsets == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
   return num_values == 1 ? DEGA_OK : check_levels_job(job, &num_values, 1, samples, &packed, &packed_cap, &offsets, &out_bits, &err, what);
 }

@@ -25,6 +25,10 @@
  *                       readers and decoders above deliver (a float matrix and a count per channel) goes into
  *                       aggregate, the DEGA float entry, `encode csv` and the LZMH chain as it is, every channel coded as
  *                       the reference codes a file of that channel's own length.
+ *   dega_hip_to_time_major_dev / dega_hip_to_channel_major_dev / DEGA_SAMPLES_CHANNEL_MAJOR   nothing of the reference's code: its
+ *                       DCCLI codes one file per meter, so its users hold C series, each contiguous (channel-major,
+ *                       [C][stride]), while every kernel here reads time-major rows.  The two calls turn one image into
+ *                       the other on the device, and the flag lets the host jobs take and return channel-major samples.
  *   the bit format       DCIOLib/src/bit_file_buffer.c:220-248, 297-308 (MSB-first bits, big-endian values).
  * The reference-side binding (a row in encoders_decoders[], DCLib/src/enc_dec.c:51-60, whose enc_dec_function_t
  * (DCLib/inc/enc_dec.h:11) pulls the stream out of in_bit_buf, calls these, and pushes the result into out_bit_buf)
@@ -40,6 +44,11 @@
  *   streams  out  : uint8 [C][cap]  channel c's stream starts at out + c*cap; cap is a multiple of 4
  *            bits : uint64 [C]      exact stream length in bits (the last byte is zero padded)
  *            err  : int32 [C]       DEGA_OK or a negative reference error code for that channel
+ *   samples  x_ct : [C][stride]     channel-major, one series after another (stride >= T elements per channel): the
+ *                                   transposition calls and, with DEGA_SAMPLES_CHANNEL_MAJOR, the host jobs.  Elements are 4
+ *                                   or 8 opaque bytes.  Only the logical C x T region is read or written: the padding of
+ *                                   either image keeps what it held.  With a count per channel, element (c, t) with
+ *                                   t >= min(count[c], T) is written as zero bits whatever its source holds.
  * "dev" entry points take DEVICE pointers and enqueue on `stream` (a hipStream_t passed as void*, NULL = default
  * stream) without synchronising.  "host" entry points take host pointers and are synchronous; inside they are a
  * pipeline over chunks of channels, and dega_hip_group_* spreads one over every GPU of the node.
@@ -74,13 +83,22 @@ typedef struct dega_hip_group dega_hip_group; /* several contexts: one per GPU o
 #define DEGA_SAMPLES_F32 3  /* float32 [T][ld] readings, valuesize 1..64: Normalize / Denormalize (DCLib/src/normalize.c:9-41)
                                run inside the encode / decode kernel, one launch per direction */
 
+/* OR-ed into `samples`: the host array is channel-major, [C][ld] with ld >= T the pitch between CHANNELS in elements, instead
+   of [T][ld] with ld >= C.  Everything else about the job is as without it.  Honoured by dega_hip_encode_job_host,
+   dega_hip_decode_job_host, dega_hip_encode_levels_job_host (and through it dega_hip_encode_agg_job_host) and their
+   dega_hip_group_* forms; every other call refuses it with DEGA_ERROR_INVALID_VALUE.  A chunk of channels goes up as it
+   lies (one contiguous copy when ld == T), is transposed on the device (dega_hip_to_time_major_dev's kernel) and coded
+   as ever; decode transposes behind the decoder and downloads into the caller's [C][ld], whose padding it leaves alone.
+   With out_count, the tail of every decoded series (t >= out_count[c]) is zero. */
+#define DEGA_SAMPLES_CHANNEL_MAJOR 0x100
+
 /* One batch of C channels x T samples for the host-pointer entry points. */
 typedef struct dega_hip_job
 {
-  size_t C, T, ld; /* channels, samples per channel, row pitch of `samples` in elements (>= C) */
+  size_t C, T, ld; /* channels, samples per channel, row pitch of `samples` in elements (>= C; channel-major: >= T) */
   int adaptive;    /* 0 = `bac`, 1 = `bac adaptive` */
   int valuesize;   /* the `valuesize` option of the stages, 1..64 */
-  int samples;     /* DEGA_SAMPLES_* */
+  int samples;     /* DEGA_SAMPLES_*, optionally | DEGA_SAMPLES_CHANNEL_MAJOR */
   float factor;    /* normalization_factor (DEGA_SAMPLES_F32 only) */
 } dega_hip_job;
 
@@ -415,6 +433,21 @@ int dega_hip_lzmh_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc
                                             const size_t *num_values, size_t K, unsigned decimals, size_t column, int separator_char,
                                             const size_t *text_stride, uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits,
                                             uint64_t *const *text_len, uint64_t *const *out_count, int32_t *const *err, void *stream);
+
+/* ---- channel-major <-> time-major, device pointers ------------------------------------------------------------------------ */
+/* x_ct [C][stride] -> x_tc [T][ld] and back: x_tc[t][c] = x_ct[c][t] for c < C, t < T, elements of elem_bytes = 4 or 8 opaque
+   bytes (float32 / int32 / big-endian int32; int64).  Nothing outside the logical region of the destination is written:
+   columns C .. ld - 1 of a time-major row and T .. stride - 1 of a channel-major row keep what they held.  count (device
+   uint64 [C], as in the ragged entry points; NULL = uniform): element (c, t) with t >= min(count[c], T) is written as
+   all-zero bits; its source element may be read but influences nothing (it may be NaN or uninitialised).  Both enqueue one
+   kernel on `stream` without synchronising; pitches may be odd and the bases need only the element's alignment (16-byte
+   loads and stores are used on each side whose base and pitch allow them).  DEGA_ERROR_INVALID_VALUE with nothing written:
+   elem_bytes other than 4 or 8, ld < C or stride < T, a pointer not aligned to the element or a count not aligned to 8,
+   source and destination ranges that overlap.  C == 0 or T == 0: DEGA_OK, nothing launched. */
+int dega_hip_to_time_major_dev(dega_hip_ctx *ctx, const void *x_ct, size_t C, size_t T, size_t stride, size_t elem_bytes, const uint64_t *count,
+                               void *x_tc, size_t ld, void *stream);
+int dega_hip_to_channel_major_dev(dega_hip_ctx *ctx, const void *x_tc, size_t C, size_t T, size_t ld, size_t elem_bytes, const uint64_t *count,
+                                  void *x_ct, size_t stride, void *stream);
 
 /* ---- host pointers: the pipelined path DCCLI's stage loop (DCCLI/src/cli.c:430-466) ends up on ---------------------------- */
 /* `samples` and the outputs are HOST memory (pageable or pinned).  The batch is cut into chunks of channels, each on a
