@@ -938,6 +938,7 @@ DG_DEV void decode_coding_wave(const DecodeArgs &a, const uint32_t *tab, uint32_
   StreamTail tail;
   tail.init(nbits, cap_words);
   const uint32_t max_seg_bits = (uint32_t)a.T * 65u; // no valid stream of T samples decodes to more bits (T <= 2^25)
+  const uint64_t bp_limit = nbits + 14u;             // at most 14 phantom bits after the stream's end (bac.c:171-186)
   // 16 bytes per lane and DMA instruction when the slabs allow it (a lane's words are 16-byte aligned, and a group of
   // four never leaves the slab); else four single words
   const bool quads = (a.cap % 16u) == 0u && (((size_t)a.in) % 16u) == 0u;
@@ -1021,6 +1022,12 @@ DG_DEV void decode_coding_wave(const DecodeArgs &a, const uint32_t *tab, uint32_
     }
     if ((peer & DEC_PUB_FINAL) != 0u)
       bac_done = true; // the parser has all it wants from this channel (or has given it up)
+    // The 15th phantom bit has been consumed: the reference refuses the stream right there (ReadBitSpecial), whatever the
+    // symbols that follow.  So does this lane -- the zeros behind a stream that was cut short decode to symbols for as
+    // long as no EOF symbol turns up among them, several samples per stream bit, and nobody wants them.
+    const bool past_end = started && !bac_done && dec.bp > bp_limit;
+    bac_done = bac_done || past_end;
+    pub_flags |= past_end ? DEC_PUB_BAD : 0u;
     const bool room = ((wr - peer) & 0xFFFFu) < DEC_BRING;
     const bool can = live && started && !bac_done && room;
     const bool can_word = can && input_ok && nacc == 0u;
@@ -1150,8 +1157,8 @@ DG_DEV void decode_coding_wave(const DecodeArgs &a, const uint32_t *tab, uint32_
             if (r == 2)
             {
               bac_done = true;
-              if (dec.bp > nbits + 14u)
-                pub_flags |= DEC_PUB_BAD; // more than 14 phantom bits (bac.c:171-186)
+              if (dec.bp > bp_limit)
+                pub_flags |= DEC_PUB_BAD; // the EOF symbol itself took the 15th phantom bit
             }
             else
             {

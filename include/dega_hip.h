@@ -140,7 +140,12 @@ int dega_hip_decode_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const 
 
 /* Like dega_hip_decode_dev, for streams whose sample count is not known (a DCLib stream has no header: the count is
    implied by the EOF symbol, bac.c:256): decodes up to max_T samples per channel and reports each channel's count in
-   out_count[c]; a channel holding more than max_T samples gets DEGA_ERROR_MEMORY (call again with more room). */
+   out_count[c]; a channel holding more than max_T samples gets DEGA_ERROR_MEMORY (call again with more room).
+   What is defined: err[c] of every channel; for a channel with err[c] == 0, out_count[c] and the rows below it.  Not
+   defined (here and in every other decode entry that reports counts): the rows at or beyond a channel's count, and the
+   count and the whole column of a channel with err[c] != 0 -- a damaged stream is given up wherever the first check
+   trips, and how much of it has been written by then depends on the waves' timing.  Nothing outside the C columns and the
+   max_T rows is ever written. */
 int dega_hip_decode_var_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t max_T, size_t ld,
                             int adaptive, int valuesize, int32_t *x_tc, uint64_t *out_count, int32_t *err, void *stream);
 

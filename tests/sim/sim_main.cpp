@@ -315,16 +315,22 @@ extern "C" __attribute__((visibility("default"))) int sim_lzmh_decode(const uint
 }
 
 // the 8-pair workgroup shape that the library uses for decoding batches of more than 64 Ki channels, forced on a small batch
-extern "C" __attribute__((visibility("default"))) int sim_decode_wide(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, int adaptive, int32_t *x, int32_t *err)
+// (counts: NULL, or up to T samples per channel and the count reported, as sim_decode_var_vs)
+extern "C" __attribute__((visibility("default"))) int sim_decode_wide_var(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, int adaptive, int32_t *x, uint64_t *counts, int32_t *err)
 {
   static const std::vector<uint32_t> tab = make_table();
-  DecodeArgs a{in, cap, in_bits, C, T, ld, x, err, tab.data(), nullptr, 32u};
+  DecodeArgs a{in, cap, in_bits, C, T, ld, x, err, tab.data(), counts, 32u};
   const dim3 grid((unsigned)((C + 511) / 512)); // 8 pairs of waves, 16-sample ring
   if (adaptive)
     sim::launch(dega_decode_kernel<true, false, false, false, 8, false>, grid, dim3(1024), a);
   else
     sim::launch(dega_decode_kernel<false, false, false, false, 8, false>, grid, dim3(1024), a);
   return 0;
+}
+
+extern "C" __attribute__((visibility("default"))) int sim_decode_wide(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, int adaptive, int32_t *x, int32_t *err)
+{
+  return sim_decode_wide_var(in, cap, in_bits, C, T, ld, adaptive, x, nullptr, err);
 }
 
 // valuesize 33..64: int64 containers
