@@ -113,6 +113,66 @@ def oracle_verdict(data, nbits, vs, ad):
     return 0, unpack_be(d, n, vs)
 
 
+def damage(rng, b, n, k, c):
+    """the stream b (a bytearray) of n bits, damaged by kind k (KINDS); c picks among kind 9's variants.  -> (bytes, bits, what
+    was done).  The bits beyond the new length keep whatever the damage left there."""
+    what = ""
+    if k in (1, 2, 3):
+        lo, hi = (0, n) if k == 1 else (0, min(64, n)) if k == 2 else (max(0, n - 16), n)
+        at = int(rng.integers(lo, hi))
+        b[at // 8] ^= 0x80 >> (at % 8)
+        what = "bit %d of %d flipped" % (at, n)
+    elif k == 4:
+        at = int(rng.integers(0, max(1, len(b) - 3)))
+        b[at: at + 4] = bytes(rng.integers(0, 256, 4, dtype=np.uint8))[: len(b) - at]
+        what = "bytes %d..%d random" % (at, at + 3)
+    elif k == 5:
+        cut = int(rng.integers(1, 41))
+        what = "%d bits shortened by %d, bytes kept" % (n, cut)
+        n = max(1, n - cut)
+    elif k == 6:
+        what = "%d bits cut" % n
+        n = int(rng.integers(1, n))
+        what += " to %d, bytes kept" % n
+    elif k == 7:
+        more = int(rng.integers(1, 65))
+        what = "%d bits lengthened by %d over zero bytes" % (n, more)
+        n += more
+        b += bytes((n + 7) // 8 - len(b))
+    elif k == 8:
+        b = bytearray(rng.integers(0, 256, len(b), dtype=np.uint8).tobytes())
+        what = "every byte random"
+    elif k == 9:
+        which = (c // 10) % 4
+        if which == 3:
+            n, what = 0, "healthy bytes, bits = 0"
+        else:
+            # (at most CONSTANT_MAX_BITS: the adaptive model decodes 0xFF bytes to thousands of seg bits per stream
+            # bit, every one of which the oracle's bac stage writes out before it refuses the stream)
+            n = min(n, CONSTANT_MAX_BITS)
+            b = bytearray([CONSTANT_BYTES[which]]) * ((n + 7) // 8)
+            what = "%d bits, every byte 0x%02X" % (n, CONSTANT_BYTES[which])
+    return b, n, what
+
+
+def slab_forms(rng, rows, bits, cap):
+    """the streams `rows` (bytes each) of `bits` bits as slabs uint8 [C][cap] in the two forms: clean, and garbage -- every bit
+    from a stream's exact length to the end of its slab random"""
+    C = len(rows)
+    clean = np.zeros((C, cap), dtype=np.uint8)
+    for c in range(C):
+        clean[c, : len(rows[c])] = np.frombuffer(rows[c], dtype=np.uint8)
+    garbage = clean.copy()
+    junk = rng.integers(0, 256, (C, cap), dtype=np.uint8)
+    for c in range(C):
+        n = int(bits[c])
+        garbage[c, (n + 7) // 8:] = junk[c, (n + 7) // 8:]
+        if n % 8:
+            keep = (0xFF00 >> (n % 8)) & 0xFF
+            garbage[c, n // 8] = (int(garbage[c, n // 8]) & keep) | (int(junk[c, n // 8]) & (0xFF ^ keep))
+    return clean, garbage
+
+
 class Corpus:
     """slabs[form] uint8 [C][cap], bits uint64 [C], kind [C], made_from[c] (a line of text), x uint64 [T][C] (the samples the
     healthy streams code), plus the oracle's verdicts, computed on first use and kept.  Arrays are read-only."""
@@ -125,43 +185,8 @@ class Corpus:
         self.kind = np.arange(C) % 10
         rows, bits, made = [], np.zeros(C, dtype=np.uint64), []
         for c in range(C):
-            b, n = bytearray(streams[c][0]), streams[c][1]
-            k, what = int(self.kind[c]), ""
-            if k in (1, 2, 3):
-                lo, hi = (0, n) if k == 1 else (0, min(64, n)) if k == 2 else (max(0, n - 16), n)
-                at = int(rng.integers(lo, hi))
-                b[at // 8] ^= 0x80 >> (at % 8)
-                what = "bit %d of %d flipped" % (at, n)
-            elif k == 4:
-                at = int(rng.integers(0, max(1, len(b) - 3)))
-                b[at: at + 4] = bytes(rng.integers(0, 256, 4, dtype=np.uint8))[: len(b) - at]
-                what = "bytes %d..%d random" % (at, at + 3)
-            elif k == 5:
-                cut = int(rng.integers(1, 41))
-                what = "%d bits shortened by %d, bytes kept" % (n, cut)
-                n = max(1, n - cut)
-            elif k == 6:
-                what = "%d bits cut" % n
-                n = int(rng.integers(1, n))
-                what += " to %d, bytes kept" % n
-            elif k == 7:
-                more = int(rng.integers(1, 65))
-                what = "%d bits lengthened by %d over zero bytes" % (n, more)
-                n += more
-                b += bytes((n + 7) // 8 - len(b))
-            elif k == 8:
-                b = bytearray(rng.integers(0, 256, len(b), dtype=np.uint8).tobytes())
-                what = "every byte random"
-            elif k == 9:
-                which = (c // 10) % 4
-                if which == 3:
-                    n, what = 0, "healthy bytes, bits = 0"
-                else:
-                    # (at most CONSTANT_MAX_BITS: the adaptive model decodes 0xFF bytes to thousands of seg bits per stream
-                    # bit, every one of which the oracle's bac stage writes out before it refuses the stream)
-                    n = min(n, CONSTANT_MAX_BITS)
-                    b = bytearray([CONSTANT_BYTES[which]]) * ((n + 7) // 8)
-                    what = "%d bits, every byte 0x%02X" % (n, CONSTANT_BYTES[which])
+            k = int(self.kind[c])
+            b, n, what = damage(rng, bytearray(streams[c][0]), streams[c][1], k, c)
             rows.append(bytes(b))
             bits[c] = n
             made.append("%s: %s" % (KINDS[k], what) if what else KINDS[k])
@@ -174,17 +199,7 @@ class Corpus:
             bits[c7] = 8 * cap
             made[c7] += ", then to the end of the slab"
         self.cap = cap
-        clean = np.zeros((C, cap), dtype=np.uint8)
-        for c in range(C):
-            clean[c, : len(rows[c])] = np.frombuffer(rows[c], dtype=np.uint8)
-        garbage = clean.copy()
-        junk = rng.integers(0, 256, (C, cap), dtype=np.uint8)
-        for c in range(C):
-            n = int(bits[c])
-            garbage[c, (n + 7) // 8:] = junk[c, (n + 7) // 8:]
-            if n % 8:
-                keep = (0xFF00 >> (n % 8)) & 0xFF
-                garbage[c, n // 8] = (int(garbage[c, n // 8]) & keep) | (int(junk[c, n // 8]) & (0xFF ^ keep))
+        clean, garbage = slab_forms(rng, rows, bits, cap)
         self.slabs = {"clean": clean, "garbage": garbage}
         self.bits, self.made_from = bits, made
         for a in (self.x, clean, garbage, bits, self.kind):

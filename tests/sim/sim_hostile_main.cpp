@@ -5,8 +5,10 @@
 //
 //   sim_hostile <corpus file> <result file>
 // corpus file: 8 x uint64 {magic, C, cap, room, valuesize, adaptive, shape (0: three waves per group, 1: wide pairs,
-//              2: 64-bit containers), drag (microseconds per step of the parsing side, 0: none)}, bits uint64 [C], slabs uint8 [C][cap]
-// result file: err int32 [C], counts uint64 [C], samples [room][C] (int32, or int64 for shape 2)
+//              2: 64-bit containers, 3: the LZMH decoder -- room is then the bytes of an output row, valuesize and adaptive
+//              are not used), drag (microseconds per step of the parsing side -- LZMH: the writing side --, 0: none)},
+//              bits uint64 [C], slabs uint8 [C][cap]
+// result file: err int32 [C], counts uint64 [C], samples [room][C] (int32, or int64 for shape 2; shape 3: bytes uint8 [C][room])
 #include "sim_main.cpp"
 
 #include <memory>
@@ -29,7 +31,7 @@ int main(int argc, char **argv)
   }
   const size_t C = head[1], cap = head[2], room = head[3];
   const int valuesize = (int)head[4], adaptive = (int)head[5], shape = (int)head[6], drag_us = (int)head[7];
-  const size_t width = shape == 2 ? 8 : 4;
+  const size_t width = shape == 2 ? 8 : shape == 3 ? 1 : 4;
   std::unique_ptr<uint64_t[]> bits(new uint64_t[C]);
   std::unique_ptr<uint8_t[]> slabs(new uint8_t[C * cap]);
   if (fread(bits.get(), sizeof(uint64_t), C, f) != C || fread(slabs.get(), 1, C * cap, f) != C * cap)
@@ -43,8 +45,10 @@ int main(int argc, char **argv)
   std::unique_ptr<uint8_t[]> x(new uint8_t[room * C * width]); // (operator new aligns for any sample type)
   memset(x.get(), 0, room * C * width);
   if (drag_us > 0)
-    sim_set_drag(shape == 1 ? 8 : 4, drag_us); // the parsing waves (and the loading waves behind them) of either workgroup shape
-  if (shape == 2)
+    sim_set_drag(shape == 1 ? 8 : 4, drag_us); // the parsing waves (and the loading waves behind them) of either workgroup shape; LZMH's writing waves
+  if (shape == 3)
+    sim_lzmh_decode(slabs.get(), cap, bits.get(), C, x.get(), room, counts.get(), err.get());
+  else if (shape == 2)
     sim_decode64(slabs.get(), cap, bits.get(), C, room, C, adaptive, valuesize, reinterpret_cast<int64_t *>(x.get()), counts.get(), err.get());
   else if (shape == 1)
     sim_decode_wide_var(slabs.get(), cap, bits.get(), C, room, C, adaptive, reinterpret_cast<int32_t *>(x.get()), counts.get(), err.get());

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from lzmh_hostile_common import longest_match_strings
 from oracle import orc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -145,11 +146,7 @@ def test_lzmh_render_kernel(sim):
 def test_lzmh_longest_match_at_every_window_alignment(sim):
     """A match of the maximum length (274) that begins at every position modulo 16: the window a lane reloads starts at
     (P - 128) rounded down to 16, and whatever the alignment it has to hold the whole match, or the step is retried for ever."""
-    rng = np.random.default_rng(3)
-    strings = []
-    for k in range(32):
-        head = bytes(rng.integers(0, 256, 130 + k, dtype=np.uint8))
-        strings.append(head + bytes([65 + k]) * (700 + 3 * k) + head[:40])
+    strings = longest_match_strings()  # (the same through the HIP encoder: tests/test_gpu_lzmh_hostile.py)
     out, bits, err = sim_encode(sim, strings)
     assert (err == 0).all()
     for i, s in enumerate(strings):
