@@ -35,6 +35,20 @@ using namespace dg;
 struct Pipeline;
 static void pipeline_destroy(Pipeline *p);
 
+// A block of device memory between the launches of one call.  The block is shared by all calls on the context, whatever
+// their streams: `done` is recorded behind every call's last launch that uses the block, and a call on another stream
+// than the last one makes its stream wait for it before its first launch writes the block (on the device; the host never
+// waits).  It grows only, by doubling, and a block it has outgrown is kept until the context goes -- freeing would
+// synchronise the device; the blocks kept back sum to less than the live one.
+struct Scratch
+{
+  uint8_t *p = nullptr;
+  size_t bytes = 0;
+  hipEvent_t done = nullptr;    // behind the last call's last launch on the block (nullptr until the first call)
+  hipStream_t stream = nullptr; // the stream that call used
+  bool pending = false;         // done has been recorded
+};
+
 struct dega_hip_ctx
 {
   int device;
@@ -45,25 +59,11 @@ struct dega_hip_ctx
   std::vector<hipEvent_t> ev_pool; // events handed back by profile_read, reused by the next timed launches
   int force_waves; // 0 = choose by batch size; 4 / 8 = pairs of waves per workgroup, DEGA_WAVES_PER_WORKGROUP (measurement knob)
   Pipeline *pipe;  // streams and buffers of the host-pointer entry points, created on first use
-  // The aggregated rows between the launches of dega_hip_encode_levels_f32_dev.  The block is shared by all calls on the
-  // context, whatever their streams: agg_done is recorded behind every call's encode launch, and a call on another
-  // stream than the last one makes its stream wait for it before its aggregate launch writes the block (on the device;
-  // the host never waits).  It grows only, by doubling, and a block it has outgrown is kept until the context goes --
-  // freeing would synchronise the device; the blocks kept back sum to less than the live one.
-  float *agg_scratch;
-  size_t agg_scratch_floats;
+  // `sums`: the aggregated rows between the launches of the level calls; `text`: the text between the launches of
+  // dega_hip_lzmh_encode_f32_dev / dega_hip_lzmh_encode_levels_f32_dev / dega_hip_lzmh_decode_f32_dev (in front of it
+  // the per-channel status and lengths, TextScratch).  Blocks they have outgrown are kept in `agg_retired`.
+  Scratch sums, text;
   std::vector<void *> agg_retired;
-  hipEvent_t agg_done;     // behind the last call's encode launch (nullptr until the first call)
-  hipStream_t agg_stream;  // the stream that call used
-  bool agg_pending;        // agg_done has been recorded
-  // The text between the launches of dega_hip_lzmh_encode_f32_dev / dega_hip_lzmh_encode_levels_f32_dev (in front of
-  // it the renderer's per-channel status and lengths): the protocol of the aggregate scratch with an event of its own,
-  // recorded behind the last launch that reads the text.  Blocks it has outgrown join agg_retired.
-  uint8_t *txt_scratch;
-  size_t txt_scratch_bytes;
-  hipEvent_t txt_done;
-  hipStream_t txt_stream;
-  bool txt_pending;
 };
 
 static int fail(dega_hip_ctx *ctx, int code, const char *what, hipError_t e)
@@ -136,16 +136,6 @@ extern "C" int dega_hip_create(int device, dega_hip_ctx **out)
   ctx->last_error[0] = '\0';
   ctx->profile = false;
   ctx->pipe = nullptr;
-  ctx->agg_scratch = nullptr;
-  ctx->agg_scratch_floats = 0;
-  ctx->agg_done = nullptr;
-  ctx->agg_stream = nullptr;
-  ctx->agg_pending = false;
-  ctx->txt_scratch = nullptr;
-  ctx->txt_scratch_bytes = 0;
-  ctx->txt_done = nullptr;
-  ctx->txt_stream = nullptr;
-  ctx->txt_pending = false;
   {
     const char *w = getenv("DEGA_WAVES_PER_WORKGROUP");
     const int v = w != nullptr ? atoi(w) : 0;
@@ -186,16 +176,15 @@ extern "C" void dega_hip_destroy(dega_hip_ctx *ctx)
   for (hipEvent_t e : ctx->ev_pool)
     (void)hipEventDestroy(e);
   (void)hipFree(ctx->div_magic);
-  if (ctx->agg_scratch != nullptr)
-    (void)hipFree(ctx->agg_scratch);
+  for (Scratch *b : {&ctx->sums, &ctx->text})
+  {
+    if (b->p != nullptr)
+      (void)hipFree(b->p);
+    if (b->done != nullptr)
+      (void)hipEventDestroy(b->done);
+  }
   for (void *p : ctx->agg_retired)
     (void)hipFree(p);
-  if (ctx->agg_done != nullptr)
-    (void)hipEventDestroy(ctx->agg_done);
-  if (ctx->txt_scratch != nullptr)
-    (void)hipFree(ctx->txt_scratch);
-  if (ctx->txt_done != nullptr)
-    (void)hipEventDestroy(ctx->txt_done);
   delete ctx;
 }
 
@@ -636,6 +625,17 @@ extern "C" size_t dega_hip_aggregate_rows(size_t T, size_t num_values)
   return num_values == 0 ? 0 : T / num_values + (T % num_values != 0 ? 1 : 0);
 }
 
+static bool f32_array(const void *p) // a float32 device array, as far as the host can tell
+{
+  return p != nullptr && ((uintptr_t)p & 3u) == 0;
+}
+
+// the bytes from the first to the last value of a [rows][ld] float32 image of C channels (rows at least 1)
+static size_t image_bytes(size_t rows, size_t ld, size_t C)
+{
+  return ((rows - 1) * ld + C) * sizeof(float);
+}
+
 // Columns x ranges of output rows (the pattern of rowsplit_grid, cut at multiples of num_values because the unit is an
 // output row): enough workgroups for eight per CU where the batch has them, never more ranges than output rows.
 static int launch_aggregate(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t N, float *a_tc, size_t ld_out, hipStream_t s)
@@ -648,13 +648,13 @@ static int launch_aggregate(dega_hip_ctx *ctx, const float *v_tc, size_t C, size
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: ld < C or ld_out < C", hipSuccess);
   if (C == 0 || T == 0)
     return DEGA_OK;
-  if (v_tc == nullptr || a_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0 || ((uintptr_t)a_tc & 3u) != 0)
+  if (!f32_array(v_tc) || !f32_array(a_tc))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: v_tc and a_tc must be float32 device arrays", hipSuccess);
   const size_t T_out = dega_hip_aggregate_rows(T, N);
   {
     // a_tc may not alias v_tc
-    const uintptr_t v0 = (uintptr_t)v_tc, v1 = v0 + ((T - 1) * ld + C) * sizeof(float);
-    const uintptr_t a0 = (uintptr_t)a_tc, a1 = a0 + ((T_out - 1) * ld_out + C) * sizeof(float);
+    const uintptr_t v0 = (uintptr_t)v_tc, v1 = v0 + image_bytes(T, ld, C);
+    const uintptr_t a0 = (uintptr_t)a_tc, a1 = a0 + image_bytes(T_out, ld_out, C);
     if (a0 < v1 && v0 < a1)
       return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: a_tc overlaps v_tc", hipSuccess);
   }
@@ -773,17 +773,35 @@ extern "C" int dega_hip_to_channel_major_dev(dega_hip_ctx *ctx, const void *x_tc
   return launch_transpose(ctx, x_tc, T, C, ld, elem_bytes, count, false, x_ct, stride, (hipStream_t)stream);
 }
 
-static int agg_scratch_need(dega_hip_ctx *ctx, size_t floats)
+// `bytes` of the block for a call on s: grown if need be, and s behind the block's last user where that was another stream.
+static int scratch_acquire(dega_hip_ctx *ctx, Scratch &b, size_t bytes, hipStream_t s)
 {
-  if (floats <= ctx->agg_scratch_floats)
-    return DEGA_OK;
-  const size_t want = std::max(floats, 2 * ctx->agg_scratch_floats); // doubling: the blocks kept back sum to less than the live one
-  float *p = nullptr;
-  HIP_TRY(ctx, hipMalloc((void **)&p, want * sizeof(float)), DEGA_ERROR_MEMORY);
-  if (ctx->agg_scratch != nullptr)
-    ctx->agg_retired.push_back(ctx->agg_scratch);
-  ctx->agg_scratch = p;
-  ctx->agg_scratch_floats = want;
+  if (bytes > b.bytes)
+  {
+    const size_t want = std::max(bytes, 2 * b.bytes); // doubling: the blocks kept back sum to less than the live one
+    uint8_t *p = nullptr;
+    HIP_TRY(ctx, hipMalloc((void **)&p, want), DEGA_ERROR_MEMORY);
+    if (b.p != nullptr)
+      ctx->agg_retired.push_back(b.p); // (a kernel may still read it: kept until the context goes)
+    b.p = p;
+    b.bytes = want;
+  }
+  if (b.done == nullptr)
+    HIP_TRY(ctx, hipEventCreateWithFlags(&b.done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
+  // the block may still be in use by a launch of an earlier call on another stream: this stream goes on behind it
+  if (b.pending && b.stream != s)
+    HIP_TRY(ctx, hipStreamWaitEvent(s, b.done, 0), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
+// The call's launches are on s: the block's event behind them, unless the caller has `recorded` it already behind the
+// block's last user.  A launcher comes here whatever its launches said.
+static int scratch_release(dega_hip_ctx *ctx, Scratch &b, hipStream_t s, bool recorded = false)
+{
+  if (!recorded)
+    HIP_TRY(ctx, hipEventRecord(b.done, s), DEGA_ERROR_LIBRARY_CALL);
+  b.stream = s;
+  b.pending = true;
   return DEGA_OK;
 }
 
@@ -799,7 +817,8 @@ extern "C" int dega_hip_encode_agg_f32_dev(dega_hip_ctx *ctx, const float *v_tc,
   return dega_hip_encode_levels_f32_dev(ctx, v_tc, C, T, ld, &num_values, 1, factor, adaptive, valuesize, &out, &cap, &out_bits, &err, stream);
 }
 
-// ---- several granularities from one pass over the base series (aggregate_levels_kernels.hpp) -------------------------------
+// ---- several granularities from one pass over the base series (aggregate_levels_kernels.hpp), for ragged batches with a
+// ---- count per channel (aggregate_var_kernels.hpp) ------------------------------------------------------------------------
 
 static_assert(DEGA_AGG_MAX_LEVELS == AGG_MAX_LEVELS, "the header's limit is the kernel's");
 
@@ -927,30 +946,6 @@ extern "C" int dega_hip_aggregate_levels_plan(size_t C, size_t T, const size_t *
   return p.passes;
 }
 
-template <uint32_t K>
-static void launch_levels_pass(const float *v_tc, size_t C, size_t T, size_t ld, size_t step, bool wide, const size_t *N, float *const *a_tc,
-                               const size_t *ld_out, hipStream_t s)
-{
-  AggregateLevelsArgs<K> a;
-  a.v = v_tc;
-  a.C = C;
-  a.T = T;
-  a.ld = ld;
-  a.step = step;
-  for (uint32_t l = 0; l < K; l++)
-  {
-    a.a[l] = a_tc[l];
-    a.ld_out[l] = ld_out[l];
-    a.N[l] = (uint32_t)std::min(N[l], T);
-    a.wide_out[l] = (wide && ld_out[l] % 4 == 0 && ((uintptr_t)a_tc[l] & 15u) == 0) ? 1u : 0u;
-  }
-  const dim3 grid((unsigned)agg_gx(C, wide), (unsigned)((T + step - 1) / step));
-  if (wide)
-    hipLaunchKernelGGL((dega_aggregate_levels_kernel<AggF4, K>), grid, dim3(AGG_BLOCK), 0, s, a);
-  else
-    hipLaunchKernelGGL((dega_aggregate_levels_kernel<float, K>), grid, dim3(AGG_BLOCK), 0, s, a);
-}
-
 // Everything launch_aggregate and the pass launches would refuse, for all levels, before the first launch.
 static int check_levels_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K, float *const *a_tc,
                             const size_t *ld_out)
@@ -970,19 +965,19 @@ static int check_levels_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size
       return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: ld_out < C", hipSuccess);
   if (C == 0 || T == 0)
     return DEGA_OK;
-  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
+  if (!f32_array(v_tc))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: v_tc must be a float32 device array", hipSuccess);
   if (agg_gx(C, false) > 0x7FFFFFFFu)
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: too many channels for one launch", hipSuccess);
   uintptr_t lo[AGG_MAX_LEVELS + 1], hi[AGG_MAX_LEVELS + 1];
   lo[K] = (uintptr_t)v_tc;
-  hi[K] = lo[K] + ((T - 1) * ld + C) * sizeof(float);
+  hi[K] = lo[K] + image_bytes(T, ld, C);
   for (size_t k = 0; k < K; k++)
   {
-    if (a_tc[k] == nullptr || ((uintptr_t)a_tc[k] & 3u) != 0)
+    if (!f32_array(a_tc[k]))
       return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: every a_tc[k] must be a float32 device array", hipSuccess);
     lo[k] = (uintptr_t)a_tc[k];
-    hi[k] = lo[k] + ((dega_hip_aggregate_rows(T, num_values[k]) - 1) * ld_out[k] + C) * sizeof(float);
+    hi[k] = lo[k] + image_bytes(dega_hip_aggregate_rows(T, num_values[k]), ld_out[k], C);
     if (lo[k] < hi[K] && lo[K] < hi[k])
       return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: an output overlaps v_tc", hipSuccess);
     for (size_t i = 0; i < k; i++)
@@ -990,161 +985,6 @@ static int check_levels_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size
         return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: two levels' outputs overlap", hipSuccess);
   }
   return DEGA_OK;
-}
-
-// The passes of the plan on s.  The arguments have been through check_levels_dev.
-static int launch_aggregate_levels(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
-                                   float *const *a_tc, const size_t *ld_out, hipStream_t s)
-{
-  if (K == 0 || C == 0 || T == 0)
-    return DEGA_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  const bool wide = C % 4 == 0 && ld % 4 == 0 && ((uintptr_t)v_tc & 15u) == 0; // as launch_aggregate
-  LevelsPlan p;
-  plan_levels(C, T, num_values, K, wide, p);
-  for (int q = 0; q < p.passes; q++)
-  {
-    size_t N[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS];
-    float *a[AGG_MAX_LEVELS];
-    uint32_t n = 0;
-    for (size_t k = 0; k < K; k++)
-      if (p.pass_of[k] == q)
-      {
-        N[n] = num_values[k];
-        a[n] = a_tc[k];
-        ldo[n] = ld_out[k];
-        n++;
-      }
-    if (n == 1) // the existing kernel and launcher, as they are
-    {
-      const int ret = launch_aggregate(ctx, v_tc, C, T, ld, N[0], a[0], ldo[0], s);
-      if (ret != DEGA_OK)
-        return ret;
-      continue;
-    }
-    const size_t step = p.step_of[q];
-    switch (n)
-    {
-      case 2: launch_levels_pass<2>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
-      case 3: launch_levels_pass<3>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
-      case 4: launch_levels_pass<4>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
-      case 5: launch_levels_pass<5>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
-      case 6: launch_levels_pass<6>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
-      case 7: launch_levels_pass<7>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
-      default: launch_levels_pass<8>(v_tc, C, T, ld, step, wide, N, a, ldo, s); break;
-    }
-    HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
-  }
-  return DEGA_OK;
-}
-
-extern "C" int dega_hip_aggregate_levels_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
-                                             float *const *a_tc, const size_t *ld_out, void *stream)
-{
-  int ret;
-  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, num_values, K, a_tc, ld_out)) != DEGA_OK)
-    return ret;
-  return launch_aggregate_levels(ctx, v_tc, C, T, ld, num_values, K, a_tc, ld_out, (hipStream_t)stream);
-}
-
-static size_t round4(size_t n)
-{
-  return (n + 3) & ~(size_t)3;
-}
-
-extern "C" int dega_hip_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
-                                              float factor, int adaptive, int valuesize, uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits,
-                                              int32_t *const *err, void *stream)
-{
-  if (ctx == nullptr)
-    return DEGA_ERROR_INVALID_VALUE;
-  if (check_level_list(num_values, K) != DEGA_OK)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: at most 8 levels, every num_values at least 1, none twice", hipSuccess);
-  if (K == 0)
-    return DEGA_OK;
-  if (out == nullptr || cap == nullptr || out_bits == nullptr || err == nullptr)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: out, cap, out_bits and err are arrays of K entries", hipSuccess);
-  int ret;
-  // every level's encode launch judged before the first launch (cap[k] and the 2^25 limit against level k's rows), and
-  // the levels that are summed (N = 1 is coded straight from v_tc)
-  Shape j[AGG_MAX_LEVELS];
-  size_t N[AGG_MAX_LEVELS], off[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, n = 0;
-  for (size_t k = 0; k < K; k++)
-  {
-    j[k] = shape_of(C, dega_hip_aggregate_rows(T, num_values[k]), ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor);
-    if ((ret = check_job_shape(ctx, j[k], cap[k])) != DEGA_OK)
-      return ret;
-    if (C != 0 && (out[k] == nullptr || out_bits[k] == nullptr || err[k] == nullptr))
-      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: null output", hipSuccess);
-    if (num_values[k] == 1)
-      continue;
-    N[n] = num_values[k];
-    off[n] = floats; // multiples of four floats: every level's sums keep the 16-byte alignment of the block
-    ldo[n] = ld;
-    floats += round4(j[k].T * ld);
-    n++;
-  }
-  if (C == 0)
-    return DEGA_OK;
-  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: v_tc must be a float32 device array", hipSuccess);
-  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  if ((ret = agg_scratch_need(ctx, std::max<size_t>(floats, 4))) != DEGA_OK)
-    return ret;
-  float *a[AGG_MAX_LEVELS];
-  for (size_t i = 0; i < n; i++)
-    a[i] = ctx->agg_scratch + off[i];
-  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, N, n, a, ldo)) != DEGA_OK)
-    return ret;
-  hipStream_t s = (hipStream_t)stream;
-  if (ctx->agg_done == nullptr)
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->agg_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
-  // the scratch may still be read by the encode launch of an earlier call on another stream: this stream goes on behind it
-  if (ctx->agg_pending && ctx->agg_stream != s)
-    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->agg_done, 0), DEGA_ERROR_LIBRARY_CALL);
-  if ((ret = launch_aggregate_levels(ctx, v_tc, C, T, ld, N, n, a, ldo, s)) == DEGA_OK)
-  {
-    size_t i = 0;
-    for (size_t k = 0; k < K && ret == DEGA_OK; k++)
-    {
-      const void *rows = num_values[k] == 1 ? (const void *)v_tc : (const void *)a[i++];
-      ret = launch_encode(ctx, rows, j[k], C, out[k], cap[k], out_bits[k], err[k], s);
-    }
-  }
-  // (recorded whatever the launches said: behind the LAST encode launch that is on the stream)
-  HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
-  ctx->agg_stream = s;
-  ctx->agg_pending = true;
-  return ret;
-}
-
-// ---- ragged batches: a count per channel (aggregate_var_kernels.hpp) ----------------------------------------------------------
-
-template <uint32_t K>
-static void launch_var_pass(const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, size_t step, bool wide, const size_t *N,
-                            float *const *a_tc, const size_t *ld_out, uint64_t *const *out_count, int32_t *err, hipStream_t s)
-{
-  AggregateVarArgs<K> a;
-  a.v = v_tc;
-  a.C = C;
-  a.T = T;
-  a.ld = ld;
-  a.step = step;
-  a.count = count;
-  a.err = err;
-  for (uint32_t l = 0; l < K; l++)
-  {
-    a.a[l] = a_tc[l];
-    a.ld_out[l] = ld_out[l];
-    a.N[l] = (uint32_t)std::min(N[l], std::max<size_t>(T, 1));
-    a.wide_out[l] = (wide && ld_out[l] % 4 == 0 && ((uintptr_t)a_tc[l] & 15u) == 0) ? 1u : 0u;
-    a.out_count[l] = out_count[l];
-  }
-  const dim3 grid((unsigned)agg_gx(C, wide), (unsigned)std::max<size_t>(1, (T + step - 1) / step));
-  if (wide)
-    hipLaunchKernelGGL((dega_aggregate_var_kernel<AggF4, K>), grid, dim3(AGG_BLOCK), 0, s, a);
-  else
-    hipLaunchKernelGGL((dega_aggregate_var_kernel<float, K>), grid, dim3(AGG_BLOCK), 0, s, a);
 }
 
 // what the counted entry points add to their uniform twins' refusals
@@ -1166,12 +1006,49 @@ static int check_counts(dega_hip_ctx *ctx, size_t C, size_t T, const uint64_t *c
   return DEGA_OK;
 }
 
-// The passes of the plan (planned on T, as for the uniform call) through the counted kernel, on s.  The arguments have
-// been through check_levels_dev and check_counts; T = 0 still launches: the counts and the status are the kernel's.
-static int launch_aggregate_levels_var(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, const size_t *num_values,
-                                       size_t K, float *const *a_tc, const size_t *ld_out, uint64_t *const *out_count, int32_t *err, hipStream_t s)
+// f(std::integral_constant<uint32_t, n>()) for the n = 1 .. AGG_MAX_LEVELS levels of a pass
+template <typename F>
+static void for_levels_of_pass(uint32_t n, F &&f)
 {
-  if (K == 0 || C == 0)
+  switch (n)
+  {
+    case 1: f(std::integral_constant<uint32_t, 1>()); break;
+    case 2: f(std::integral_constant<uint32_t, 2>()); break;
+    case 3: f(std::integral_constant<uint32_t, 3>()); break;
+    case 4: f(std::integral_constant<uint32_t, 4>()); break;
+    case 5: f(std::integral_constant<uint32_t, 5>()); break;
+    case 6: f(std::integral_constant<uint32_t, 6>()); break;
+    case 7: f(std::integral_constant<uint32_t, 7>()); break;
+    default: f(std::integral_constant<uint32_t, 8>()); break;
+  }
+}
+
+// what AggregateLevelsArgs<n> and AggregateVarArgs<n> share: the image and the n levels of the pass
+template <typename Args>
+static void fill_pass(Args &a, uint32_t n, const float *v_tc, size_t C, size_t T, size_t ld, size_t step, bool wide, const size_t *N, float *const *a_tc,
+                      const size_t *ld_out)
+{
+  a.v = v_tc;
+  a.C = C;
+  a.T = T;
+  a.ld = ld;
+  a.step = step;
+  for (uint32_t l = 0; l < n; l++)
+  {
+    a.a[l] = a_tc[l];
+    a.ld_out[l] = ld_out[l];
+    a.N[l] = (uint32_t)std::min(N[l], std::max<size_t>(T, 1));
+    a.wide_out[l] = (wide && ld_out[l] % 4 == 0 && ((uintptr_t)a_tc[l] & 15u) == 0) ? 1u : 0u;
+  }
+}
+
+// The passes of the plan on s.  `count`, `out_count` and `err` are null for a uniform batch; with them the passes (planned
+// on T, as for the uniform call) go through the counted kernel.  The arguments have been through check_levels_dev and,
+// for a counted batch, check_counts.
+static int launch_aggregate_levels(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, const size_t *num_values,
+                                   size_t K, float *const *a_tc, const size_t *ld_out, uint64_t *const *out_count, int32_t *err, hipStream_t s)
+{
+  if (K == 0 || C == 0 || (T == 0 && count == nullptr)) // (a counted batch still launches at T = 0: the counts and the status are the kernel's)
     return DEGA_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
   const bool wide = C % 4 == 0 && ld % 4 == 0 && ((uintptr_t)v_tc & 15u) == 0; // as launch_aggregate
@@ -1189,50 +1066,135 @@ static int launch_aggregate_levels_var(dega_hip_ctx *ctx, const float *v_tc, siz
         N[n] = num_values[k];
         a[n] = a_tc[k];
         ldo[n] = ld_out[k];
-        oc[n] = out_count[k];
+        oc[n] = count != nullptr ? out_count[k] : nullptr;
         n++;
       }
-    const size_t step = std::max<size_t>(p.step_of[q], 1);
-    int32_t *const e = q == 0 ? err : nullptr; // the status is one pass's to write
-    switch (n)
+    if (count == nullptr && n == 1) // the existing kernel and launcher, as they are
     {
-      case 1: launch_var_pass<1>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
-      case 2: launch_var_pass<2>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
-      case 3: launch_var_pass<3>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
-      case 4: launch_var_pass<4>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
-      case 5: launch_var_pass<5>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
-      case 6: launch_var_pass<6>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
-      case 7: launch_var_pass<7>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
-      default: launch_var_pass<8>(v_tc, C, T, ld, count, step, wide, N, a, ldo, oc, e, s); break;
+      const int ret = launch_aggregate(ctx, v_tc, C, T, ld, N[0], a[0], ldo[0], s);
+      if (ret != DEGA_OK)
+        return ret;
+      continue;
     }
+    for_levels_of_pass(n, [&](auto levels) {
+      constexpr uint32_t NL = decltype(levels)::value;
+      if (count != nullptr)
+      {
+        AggregateVarArgs<NL> g;
+        const size_t step = std::max<size_t>(p.step_of[q], 1);
+        fill_pass(g, NL, v_tc, C, T, ld, step, wide, N, a, ldo);
+        g.count = count;
+        g.err = q == 0 ? err : nullptr; // the status is one pass's to write
+        for (uint32_t l = 0; l < NL; l++)
+          g.out_count[l] = oc[l];
+        const dim3 grid((unsigned)agg_gx(C, wide), (unsigned)std::max<size_t>(1, (T + step - 1) / step));
+        if (wide)
+          hipLaunchKernelGGL((dega_aggregate_var_kernel<AggF4, NL>), grid, dim3(AGG_BLOCK), 0, s, g);
+        else
+          hipLaunchKernelGGL((dega_aggregate_var_kernel<float, NL>), grid, dim3(AGG_BLOCK), 0, s, g);
+      }
+      else if constexpr (NL >= 2)
+      {
+        AggregateLevelsArgs<NL> g;
+        const size_t step = p.step_of[q];
+        fill_pass(g, NL, v_tc, C, T, ld, step, wide, N, a, ldo);
+        const dim3 grid((unsigned)agg_gx(C, wide), (unsigned)((T + step - 1) / step));
+        if (wide)
+          hipLaunchKernelGGL((dega_aggregate_levels_kernel<AggF4, NL>), grid, dim3(AGG_BLOCK), 0, s, g);
+        else
+          hipLaunchKernelGGL((dega_aggregate_levels_kernel<float, NL>), grid, dim3(AGG_BLOCK), 0, s, g);
+      }
+    });
     HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   }
   return DEGA_OK;
+}
+
+// One body for the uniform and the counted ("ragged", aggregate_var_kernels.hpp) form of each level call.  `counted`: the
+// call came through a counted entry point; its `count` may still be null, which check_counts refuses where C is not 0, so
+// past that check `count != nullptr` says the same.
+static int aggregate_levels(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, bool counted, const uint64_t *count,
+                            const size_t *num_values, size_t K, float *const *a_tc, const size_t *ld_out, uint64_t *const *out_count, int32_t *err,
+                            hipStream_t s)
+{
+  int ret;
+  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, num_values, K, a_tc, ld_out)) != DEGA_OK)
+    return ret;
+  if (counted)
+  {
+    if (K == 0)
+      return DEGA_OK;
+    if ((ret = check_counts(ctx, C, T, count, out_count, K, err)) != DEGA_OK)
+      return ret;
+  }
+  return launch_aggregate_levels(ctx, v_tc, C, T, ld, count, num_values, K, a_tc, ld_out, out_count, err, s);
+}
+
+extern "C" int dega_hip_aggregate_levels_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
+                                             float *const *a_tc, const size_t *ld_out, void *stream)
+{
+  return aggregate_levels(ctx, v_tc, C, T, ld, false, nullptr, num_values, K, a_tc, ld_out, nullptr, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int dega_hip_aggregate_levels_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
                                                  const size_t *num_values, size_t K, float *const *a_tc, const size_t *ld_out, uint64_t *const *out_count,
                                                  int32_t *err, void *stream)
 {
-  int ret;
-  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, num_values, K, a_tc, ld_out)) != DEGA_OK)
-    return ret;
-  if (K == 0)
-    return DEGA_OK;
-  if ((ret = check_counts(ctx, C, T, count, out_count, K, err)) != DEGA_OK)
-    return ret;
-  return launch_aggregate_levels_var(ctx, v_tc, C, T, ld, count, num_values, K, a_tc, ld_out, out_count, err, (hipStream_t)stream);
+  return aggregate_levels(ctx, v_tc, C, T, ld, true, count, num_values, K, a_tc, ld_out, out_count, err, (hipStream_t)stream);
 }
 
-// err[c] = first[c] where that is set (a count above T, found by the aggregate pass): the level's own status otherwise
-__global__ void __launch_bounds__(256) dega_first_status_kernel(const int32_t *first, size_t C, int32_t *err, uint64_t *out_bits)
+static size_t round4(size_t n)
+{
+  return (n + 3) & ~(size_t)3;
+}
+
+// The summed levels of a call, one behind the other in a block of floats with pitch ld: level i of them is the caller's
+// level `level[i]`, off[i] floats into the block.  The offsets are multiples of four floats: every level's sums keep the
+// 16-byte alignment of the block.  A level with num_values 1 is summed only where the caller asks for it (`with_one`).
+struct LevelSums
+{
+  size_t n = 0, floats = 0;
+  size_t level[AGG_MAX_LEVELS], N[AGG_MAX_LEVELS], off[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS];
+  float *a[AGG_MAX_LEVELS];
+  LevelSums(const size_t *num_values, size_t K, size_t T, size_t ld, bool with_one)
+  {
+    for (size_t k = 0; k < K; k++)
+    {
+      if (num_values[k] == 1 && !with_one)
+        continue;
+      level[n] = k;
+      N[n] = num_values[k];
+      off[n] = floats;
+      ldo[n] = ld;
+      floats += round4(dega_hip_aggregate_rows(T, num_values[k]) * ld);
+      n++;
+    }
+  }
+  void place(float *block)
+  {
+    for (size_t i = 0; i < n; i++)
+      a[i] = block + off[i];
+  }
+};
+
+// err[c] = src[c] where that is set, and the channel's 64-bit result (its bits or its count) 0: a channel that an earlier
+// launch of the chain gave up reports that launch's status and nothing else
+__global__ void __launch_bounds__(256) dega_status_kernel(const int32_t *src, size_t C, int32_t *err, uint64_t *result)
 {
   const size_t c = (size_t)blockIdx.x * 256u + threadIdx.x;
-  if (c < C && first[c] != 0)
+  if (c < C && src[c] != 0)
   {
-    err[c] = first[c];
-    out_bits[c] = 0;
+    err[c] = src[c];
+    result[c] = 0;
   }
+}
+
+// (no HIP_TRY: a launcher that is told of a failed launch still has its event to record)
+static int launch_status(dega_hip_ctx *ctx, const int32_t *src, size_t C, int32_t *err, uint64_t *result, hipStream_t s)
+{
+  hipLaunchKernelGGL(dega_status_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, src, C, err, result);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DEGA_OK : fail(ctx, DEGA_ERROR_LIBRARY_CALL, "hipLaunchKernel", e);
 }
 
 // a level with num_values 1 is coded from the readings: its counts are the caller's, 0 where one is above T
@@ -1243,9 +1205,10 @@ __global__ void __launch_bounds__(256) dega_level_counts_kernel(const uint64_t *
     out_count[c] = count[c] > T ? 0u : count[c];
 }
 
-extern "C" int dega_hip_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
-                                                  const size_t *num_values, size_t K, float factor, int adaptive, int valuesize, uint8_t *const *out,
-                                                  const size_t *cap, uint64_t *const *out_bits, uint64_t *const *out_count, int32_t *const *err, void *stream)
+// `counted` as in aggregate_levels
+static int encode_levels(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, bool counted, const uint64_t *count, const size_t *num_values,
+                         size_t K, float factor, int adaptive, int valuesize, uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits,
+                         uint64_t *const *out_count, int32_t *const *err, hipStream_t s)
 {
   if (ctx == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
@@ -1253,77 +1216,77 @@ extern "C" int dega_hip_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const float
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: at most 8 levels, every num_values at least 1, none twice", hipSuccess);
   if (K == 0)
     return DEGA_OK;
-  if (out == nullptr || cap == nullptr || out_bits == nullptr || err == nullptr || out_count == nullptr)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: out, cap, out_bits, out_count and err are arrays of K entries", hipSuccess);
+  if (out == nullptr || cap == nullptr || out_bits == nullptr || err == nullptr || (counted && out_count == nullptr))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE,
+                counted ? "encode levels: out, cap, out_bits, out_count and err are arrays of K entries"
+                        : "encode levels: out, cap, out_bits and err are arrays of K entries",
+                hipSuccess);
   int ret;
-  // as dega_hip_encode_levels_f32_dev: every level judged before the first launch, on the rows T allows
+  // every level's encode launch judged before the first launch (cap[k] and the 2^25 limit against level k's rows, for a
+  // counted batch the rows T allows), and the levels that are summed (N = 1 is coded straight from v_tc)
   Shape j[AGG_MAX_LEVELS];
-  size_t N[AGG_MAX_LEVELS], off[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, n = 0;
-  uint64_t *oc[AGG_MAX_LEVELS];
   for (size_t k = 0; k < K; k++)
   {
     j[k] = shape_of(C, dega_hip_aggregate_rows(T, num_values[k]), ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor);
     if ((ret = check_job_shape(ctx, j[k], cap[k])) != DEGA_OK)
       return ret;
-    if (C != 0 && (out[k] == nullptr || out_bits[k] == nullptr || err[k] == nullptr || ((uintptr_t)err[k] & 3u) != 0))
+    if (C != 0 && (out[k] == nullptr || out_bits[k] == nullptr || err[k] == nullptr || (counted && ((uintptr_t)err[k] & 3u) != 0)))
       return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: null output", hipSuccess);
-    if (num_values[k] == 1)
-      continue;
-    N[n] = num_values[k];
-    off[n] = floats;
-    ldo[n] = ld;
-    oc[n] = out_count[k];
-    floats += round4(j[k].T * ld);
-    n++;
   }
+  LevelSums sums(num_values, K, T, ld, false);
   if (C == 0)
     return DEGA_OK;
-  if ((ret = check_counts(ctx, C, T, count, out_count, K, err[0])) != DEGA_OK)
+  if (counted && (ret = check_counts(ctx, C, T, count, out_count, K, err[0])) != DEGA_OK)
     return ret;
-  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
+  if (!f32_array(v_tc))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode levels: v_tc must be a float32 device array", hipSuccess);
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  // the summed levels' common status (a count above T) in front of their sums
-  const size_t head = round4(C);
-  if ((ret = agg_scratch_need(ctx, head + std::max<size_t>(floats, 4))) != DEGA_OK)
+  // a counted batch: the summed levels' common status (a count above T) in front of their sums
+  const size_t head = count != nullptr ? round4(C) : 0;
+  if ((ret = scratch_acquire(ctx, ctx->sums, (head + std::max<size_t>(sums.floats, 4)) * sizeof(float), s)) != DEGA_OK)
     return ret;
-  int32_t *const first = (int32_t *)ctx->agg_scratch;
-  float *a[AGG_MAX_LEVELS];
-  for (size_t i = 0; i < n; i++)
-    a[i] = ctx->agg_scratch + head + off[i];
-  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, N, n, a, ldo)) != DEGA_OK)
+  int32_t *const first = count != nullptr ? (int32_t *)ctx->sums.p : nullptr;
+  sums.place((float *)ctx->sums.p + head);
+  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, sums.N, sums.n, sums.a, sums.ldo)) != DEGA_OK)
     return ret;
-  hipStream_t s = (hipStream_t)stream;
-  if (ctx->agg_done == nullptr)
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->agg_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
-  if (ctx->agg_pending && ctx->agg_stream != s)
-    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->agg_done, 0), DEGA_ERROR_LIBRARY_CALL);
-  if ((ret = launch_aggregate_levels_var(ctx, v_tc, C, T, ld, count, N, n, a, ldo, oc, first, s)) == DEGA_OK)
+  uint64_t *oc[AGG_MAX_LEVELS];
+  for (size_t i = 0; i < sums.n && count != nullptr; i++)
+    oc[i] = out_count[sums.level[i]];
+  if ((ret = launch_aggregate_levels(ctx, v_tc, C, T, ld, count, sums.N, sums.n, sums.a, sums.ldo, oc, first, s)) == DEGA_OK)
   {
     size_t i = 0;
     for (size_t k = 0; k < K && ret == DEGA_OK; k++)
     {
-      if (num_values[k] == 1) // coded from v_tc with `count` itself
+      if (num_values[k] == 1)
       {
-        hipLaunchKernelGGL(dega_level_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, count, C, T, out_count[k]);
+        if (count != nullptr) // coded from v_tc with `count` itself
+          hipLaunchKernelGGL(dega_level_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, count, C, T, out_count[k]);
         ret = launch_encode(ctx, v_tc, j[k], C, out[k], cap[k], out_bits[k], err[k], s, nullptr, 0, count);
         continue;
       }
-      // (a channel whose count is above T has level counts of 0: it is coded as empty, and the status launch names it)
-      ret = launch_encode(ctx, a[i++], j[k], C, out[k], cap[k], out_bits[k], err[k], s, nullptr, 0, out_count[k]);
-      if (ret == DEGA_OK)
-      {
-        hipLaunchKernelGGL(dega_first_status_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, first, C, err[k], out_bits[k]);
-        if (hipGetLastError() != hipSuccess)
-          ret = fail(ctx, DEGA_ERROR_LIBRARY_CALL, "hipLaunchKernel", hipSuccess);
-      }
+      // (counted: a channel whose count is above T has level counts of 0: it is coded as empty, and the status launch names it)
+      ret = launch_encode(ctx, sums.a[i++], j[k], C, out[k], cap[k], out_bits[k], err[k], s, nullptr, 0, count != nullptr ? out_count[k] : nullptr);
+      if (count != nullptr && ret == DEGA_OK)
+        ret = launch_status(ctx, first, C, err[k], out_bits[k], s);
     }
   }
-  // (recorded whatever the launches said: behind the LAST launch that reads the scratch)
-  HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
-  ctx->agg_stream = s;
-  ctx->agg_pending = true;
-  return ret;
+  // (recorded whatever the launches said: behind the LAST launch on the stream that reads the scratch)
+  const int rel = scratch_release(ctx, ctx->sums, s);
+  return rel != DEGA_OK ? rel : ret;
+}
+
+extern "C" int dega_hip_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
+                                              float factor, int adaptive, int valuesize, uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits,
+                                              int32_t *const *err, void *stream)
+{
+  return encode_levels(ctx, v_tc, C, T, ld, false, nullptr, num_values, K, factor, adaptive, valuesize, out, cap, out_bits, nullptr, err, (hipStream_t)stream);
+}
+
+extern "C" int dega_hip_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
+                                                  const size_t *num_values, size_t K, float factor, int adaptive, int valuesize, uint8_t *const *out,
+                                                  const size_t *cap, uint64_t *const *out_bits, uint64_t *const *out_count, int32_t *const *err, void *stream)
+{
+  return encode_levels(ctx, v_tc, C, T, ld, true, count, num_values, K, factor, adaptive, valuesize, out, cap, out_bits, out_count, err, (hipStream_t)stream);
 }
 
 // exclusive prefix sum of ceil(bits/8) over channels: one block, chunked (C is at most a few million; not a hot path)
@@ -1583,8 +1546,9 @@ static int launch_csv(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, 
   return DEGA_OK;
 }
 
-extern "C" int dega_hip_csv_write_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column,
-                                      int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, void *stream)
+// `counted` as in aggregate_levels
+static int csv_write(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, bool counted, const uint64_t *count, unsigned decimals,
+                     size_t column, int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, hipStream_t s)
 {
   if (ctx == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
@@ -1597,55 +1561,33 @@ extern "C" int dega_hip_csv_write_dev(dega_hip_ctx *ctx, const float *v_tc, size
     return DEGA_OK;
   if (out == nullptr || out_len == nullptr || err == nullptr || ((uintptr_t)out_len & 7u) != 0 || ((uintptr_t)err & 3u) != 0)
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out, out_len and err must be device arrays", hipSuccess);
+  if (counted && (ret = check_counts(ctx, C, T, count, nullptr, 0, err)) != DEGA_OK)
+    return ret;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  hipStream_t s = (hipStream_t)stream;
-  if (T == 0) // no reading, no text: lengths 0, nothing launched
+  if (T == 0 && count == nullptr) // no reading, no text: lengths 0, nothing launched
   {
     HIP_TRY(ctx, hipMemsetAsync(out_len, 0, C * sizeof(uint64_t), s), DEGA_ERROR_LIBRARY_CALL);
     HIP_TRY(ctx, hipMemsetAsync(err, 0, C * sizeof(int32_t), s), DEGA_ERROR_LIBRARY_CALL);
     return DEGA_OK;
   }
-  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
+  if (T != 0 && !f32_array(v_tc))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: v_tc must be a float32 device array", hipSuccess);
-  if (ranges_overlap(out, C * stride, v_tc, ((T - 1) * ld + C) * sizeof(float)))
+  if (T != 0 && ranges_overlap(out, C * stride, v_tc, image_bytes(T, ld, C)))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out overlaps v_tc", hipSuccess);
-  return launch_csv(ctx, v_tc, C, T, ld, decimals, column, separator_char, out, stride, out_len, err, s);
+  // (a counted batch still launches at T = 0: a count above it is the kernel's to report)
+  return launch_csv(ctx, v_tc, C, T, ld, decimals, column, separator_char, out, stride, out_len, err, s, count);
+}
+
+extern "C" int dega_hip_csv_write_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column,
+                                      int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, void *stream)
+{
+  return csv_write(ctx, v_tc, C, T, ld, false, nullptr, decimals, column, separator_char, out, stride, out_len, err, (hipStream_t)stream);
 }
 
 extern "C" int dega_hip_csv_write_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, unsigned decimals,
                                           size_t column, int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, void *stream)
 {
-  if (ctx == nullptr)
-    return DEGA_ERROR_INVALID_VALUE;
-  int ret;
-  if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, stride)) != DEGA_OK)
-    return ret;
-  if (!aligned16(out))
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out must be 16-byte aligned", hipSuccess);
-  if (C == 0)
-    return DEGA_OK;
-  if (out == nullptr || out_len == nullptr || err == nullptr || ((uintptr_t)out_len & 7u) != 0 || ((uintptr_t)err & 3u) != 0)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out, out_len and err must be device arrays", hipSuccess);
-  if ((ret = check_counts(ctx, C, T, count, nullptr, 0, err)) != DEGA_OK)
-    return ret;
-  if (T != 0 && (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0))
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: v_tc must be a float32 device array", hipSuccess);
-  if (T != 0 && ranges_overlap(out, C * stride, v_tc, ((T - 1) * ld + C) * sizeof(float)))
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out overlaps v_tc", hipSuccess);
-  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  // (T = 0 still launches: a count above it is the kernel's to report)
-  return launch_csv(ctx, v_tc, C, T, ld, decimals, column, separator_char, out, stride, out_len, err, (hipStream_t)stream, count);
-}
-
-// A channel whose text did not fit its row was coded as the empty text: it reports the renderer's status and no stream.
-__global__ void __launch_bounds__(256) dega_csv_status_kernel(const int32_t *csv_err, size_t C, int32_t *err, uint64_t *out_bits)
-{
-  const size_t c = (size_t)blockIdx.x * 256u + threadIdx.x;
-  if (c < C && csv_err[c] != 0)
-  {
-    err[c] = csv_err[c];
-    out_bits[c] = 0;
-  }
+  return csv_write(ctx, v_tc, C, T, ld, true, count, decimals, column, separator_char, out, stride, out_len, err, (hipStream_t)stream);
 }
 
 static size_t round16(size_t n)
@@ -1653,7 +1595,8 @@ static size_t round16(size_t n)
   return (n + 15) & ~(size_t)15;
 }
 
-// The text scratch: [C] int32 renderer status | [C] uint64 text lengths | [C][text_stride] text, each 16-byte aligned.
+// The text scratch: [C] int32 status of the launch that writes the text | [C] uint64 text lengths | [C][text_stride] text,
+// each 16-byte aligned.
 struct TextScratch
 {
   int32_t *csv_err;
@@ -1661,25 +1604,18 @@ struct TextScratch
   uint8_t *text;
 };
 
-static int txt_scratch_need(dega_hip_ctx *ctx, size_t C, size_t text_stride, TextScratch &t)
+// the context's text block for C channels of text_stride bytes, for a call on s (scratch_acquire), and its parts
+static int text_scratch_acquire(dega_hip_ctx *ctx, size_t C, size_t text_stride, hipStream_t s, TextScratch &t)
 {
   const size_t head = round16(C * sizeof(int32_t)) + round16(C * sizeof(uint64_t));
   if (C > (SIZE_MAX - head) / text_stride)
     return fail(ctx, DEGA_ERROR_MEMORY, "csv: the text of the batch does not fit the address space", hipSuccess);
-  const size_t bytes = head + C * text_stride;
-  if (bytes > ctx->txt_scratch_bytes)
-  {
-    const size_t want = std::max(bytes, 2 * ctx->txt_scratch_bytes); // grow-only, by doubling: the protocol of agg_scratch_need
-    uint8_t *p = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&p, want), DEGA_ERROR_MEMORY);
-    if (ctx->txt_scratch != nullptr)
-      ctx->agg_retired.push_back(ctx->txt_scratch); // (a kernel may still read it: kept until the context goes)
-    ctx->txt_scratch = p;
-    ctx->txt_scratch_bytes = want;
-  }
-  t.csv_err = (int32_t *)ctx->txt_scratch;
-  t.len = (uint64_t *)(ctx->txt_scratch + round16(C * sizeof(int32_t)));
-  t.text = ctx->txt_scratch + head;
+  const int ret = scratch_acquire(ctx, ctx->text, head + C * text_stride, s);
+  if (ret != DEGA_OK)
+    return ret;
+  t.csv_err = (int32_t *)ctx->text.p;
+  t.len = (uint64_t *)(ctx->text.p + round16(C * sizeof(int32_t)));
+  t.text = ctx->text.p + head;
   return DEGA_OK;
 }
 
@@ -1707,9 +1643,8 @@ static int launch_csv_lzmh(dega_hip_ctx *ctx, const float *rows, size_t C, size_
     HIP_TRY(ctx, hipEventRecord(rows_read, s), DEGA_ERROR_LIBRARY_CALL);
   if ((ret = dega_hip_lzmh_encode_dev(ctx, t.text, text_stride, len, C, out, cap, out_bits, err, s)) != DEGA_OK)
     return ret;
-  hipLaunchKernelGGL(dega_csv_status_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, t.csv_err, C, err, out_bits);
-  HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
-  return DEGA_OK;
+  // A channel whose text did not fit its row was coded as the empty text: it reports the renderer's status and no stream.
+  return launch_status(ctx, t.csv_err, C, err, out_bits, s);
 }
 
 static int zero_lzmh_outputs(dega_hip_ctx *ctx, size_t C, uint64_t *out_bits, uint64_t *text_len, int32_t *err, hipStream_t s)
@@ -1738,33 +1673,29 @@ extern "C" int dega_hip_lzmh_encode_f32_dev(dega_hip_ctx *ctx, const float *v_tc
   hipStream_t s = (hipStream_t)stream;
   if (T == 0)
     return zero_lzmh_outputs(ctx, C, out_bits, text_len, err, s);
-  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
+  if (!f32_array(v_tc))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: v_tc must be a float32 device array", hipSuccess);
-  if (ranges_overlap(out, C * cap, v_tc, ((T - 1) * ld + C) * sizeof(float)))
+  if (ranges_overlap(out, C * cap, v_tc, image_bytes(T, ld, C)))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode: out overlaps v_tc", hipSuccess);
   TextScratch t;
-  if ((ret = txt_scratch_need(ctx, C, text_stride, t)) != DEGA_OK)
+  if ((ret = text_scratch_acquire(ctx, C, text_stride, s, t)) != DEGA_OK)
     return ret;
-  if (ctx->txt_done == nullptr)
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txt_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
-  // the text may still be read by the LZMH launch of an earlier call on another stream: this stream goes on behind it
-  if (ctx->txt_pending && ctx->txt_stream != s)
-    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->txt_done, 0), DEGA_ERROR_LIBRARY_CALL);
   bool rendered = false;
   ret = launch_csv_lzmh(ctx, v_tc, C, T, ld, decimals, column, separator_char, t, text_stride, out, cap, out_bits, text_len, err, s, &rendered, nullptr);
   if (rendered) // (whatever the later launches said: the renderer is on the stream and writes the scratch)
   {
-    HIP_TRY(ctx, hipEventRecord(ctx->txt_done, s), DEGA_ERROR_LIBRARY_CALL);
-    ctx->txt_stream = s;
-    ctx->txt_pending = true;
+    const int rel = scratch_release(ctx, ctx->text, s);
+    if (rel != DEGA_OK)
+      return rel;
   }
   return ret;
 }
 
-extern "C" int dega_hip_lzmh_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
-                                                   unsigned decimals, size_t column, int separator_char, const size_t *text_stride, uint8_t *const *out,
-                                                   const size_t *cap, uint64_t *const *out_bits, uint64_t *const *text_len, int32_t *const *err,
-                                                   void *stream)
+// `counted` as in aggregate_levels
+static int lzmh_encode_levels(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, bool counted, const uint64_t *count,
+                              const size_t *num_values, size_t K, unsigned decimals, size_t column, int separator_char, const size_t *text_stride,
+                              uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits, uint64_t *const *text_len, uint64_t *const *out_count,
+                              int32_t *const *err, hipStream_t s)
 {
   if (ctx == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
@@ -1772,10 +1703,13 @@ extern "C" int dega_hip_lzmh_encode_levels_f32_dev(dega_hip_ctx *ctx, const floa
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: at most 8 levels, every num_values at least 1, none twice", hipSuccess);
   if (K == 0)
     return DEGA_OK;
-  if (text_stride == nullptr || out == nullptr || cap == nullptr || out_bits == nullptr || err == nullptr)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: text_stride, out, cap, out_bits and err are arrays of K entries", hipSuccess);
+  if (text_stride == nullptr || out == nullptr || cap == nullptr || out_bits == nullptr || err == nullptr || (counted && out_count == nullptr))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE,
+                counted ? "lzmh encode levels: text_stride, out, cap, out_bits, out_count and err are arrays of K entries"
+                        : "lzmh encode levels: text_stride, out, cap, out_bits and err are arrays of K entries",
+                hipSuccess);
   int ret;
-  size_t rows[AGG_MAX_LEVELS], off[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, widest = 0;
+  size_t widest = 0;
   for (size_t k = 0; k < K; k++) // every level judged before the first launch
   {
     if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, text_stride[k])) != DEGA_OK)
@@ -1785,67 +1719,70 @@ extern "C" int dega_hip_lzmh_encode_levels_f32_dev(dega_hip_ctx *ctx, const floa
     for (size_t i = 0; i < k; i++)
       if (ranges_overlap(out[k], C * cap[k], out[i], C * cap[i]))
         return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: two levels' outputs overlap", hipSuccess);
-    rows[k] = dega_hip_aggregate_rows(T, num_values[k]);
-    off[k] = floats; // multiples of four floats, as dega_hip_encode_levels_f32_dev lays them out
-    ldo[k] = ld;
-    floats += round4(rows[k] * ld);
     widest = std::max(widest, text_stride[k]);
   }
+  // every level through the aggregate stage, num_values 1 included: the chain has `aggregate` in it (+0.0f + v)
+  LevelSums sums(num_values, K, T, ld, true);
   if (C == 0)
     return DEGA_OK;
+  if (counted)
+  {
+    if ((ret = check_counts(ctx, C, T, count, out_count, K, err[0])) != DEGA_OK)
+      return ret;
+    for (size_t k = 0; k < K; k++)
+      if (((uintptr_t)err[k] & 3u) != 0 || ((uintptr_t)out_bits[k] & 7u) != 0)
+        return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: misaligned output", hipSuccess);
+  }
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  hipStream_t s = (hipStream_t)stream;
-  if (T == 0)
+  if (T == 0 && count == nullptr)
   {
     for (size_t k = 0; k < K; k++)
       if ((ret = zero_lzmh_outputs(ctx, C, out_bits[k], text_len != nullptr ? text_len[k] : nullptr, err[k], s)) != DEGA_OK)
         return ret;
     return DEGA_OK;
   }
-  if (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0)
+  // (a counted batch still launches at T = 0, where v_tc may be null)
+  if (T != 0 && !f32_array(v_tc))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: v_tc must be a float32 device array", hipSuccess);
-  for (size_t k = 0; k < K; k++)
-    if (ranges_overlap(out[k], C * cap[k], v_tc, ((T - 1) * ld + C) * sizeof(float)))
+  for (size_t k = 0; k < K && T != 0; k++)
+    if (ranges_overlap(out[k], C * cap[k], v_tc, image_bytes(T, ld, C)))
       return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: an output overlaps v_tc", hipSuccess);
-  if ((ret = agg_scratch_need(ctx, std::max<size_t>(floats, 4))) != DEGA_OK)
+  const size_t head = count != nullptr ? round4(C) : 0; // a counted batch: the aggregate pass's status (a count above T) in front of the sums
+  if ((ret = scratch_acquire(ctx, ctx->sums, (head + std::max<size_t>(sums.floats, 4)) * sizeof(float), s)) != DEGA_OK)
     return ret;
-  float *a[AGG_MAX_LEVELS];
-  for (size_t k = 0; k < K; k++)
-    a[k] = ctx->agg_scratch + off[k];
-  // every level through the aggregate stage, num_values 1 included: the chain has `aggregate` in it (+0.0f + v)
-  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, num_values, K, a, ldo)) != DEGA_OK)
+  int32_t *const first = count != nullptr ? (int32_t *)ctx->sums.p : nullptr;
+  sums.place((float *)ctx->sums.p + head);
+  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, num_values, K, sums.a, sums.ldo)) != DEGA_OK)
     return ret;
   TextScratch t;
-  if ((ret = txt_scratch_need(ctx, C, widest, t)) != DEGA_OK) // the largest level's text; reused level after level in stream order
+  if ((ret = text_scratch_acquire(ctx, C, widest, s, t)) != DEGA_OK) // the largest level's text; reused level after level in stream order
     return ret;
-  if (ctx->agg_done == nullptr)
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->agg_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
-  if (ctx->txt_done == nullptr)
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txt_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
-  if (ctx->agg_pending && ctx->agg_stream != s)
-    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->agg_done, 0), DEGA_ERROR_LIBRARY_CALL);
-  if (ctx->txt_pending && ctx->txt_stream != s)
-    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->txt_done, 0), DEGA_ERROR_LIBRARY_CALL);
   bool rendered = false;
-  ret = launch_aggregate_levels(ctx, v_tc, C, T, ld, num_values, K, a, ldo, s);
+  ret = launch_aggregate_levels(ctx, v_tc, C, T, ld, count, num_values, K, sums.a, sums.ldo, out_count, first, s);
   for (size_t k = 0; k < K && ret == DEGA_OK; k++)
   {
-    ret = launch_csv_lzmh(ctx, a[k], C, rows[k], ld, decimals, column, separator_char, t, text_stride[k], out[k], cap[k], out_bits[k],
-                          text_len != nullptr ? text_len[k] : nullptr, err[k], s, &rendered, k + 1 == K ? ctx->agg_done : nullptr);
+    // uniform: the sums' event behind the last renderer, their last reader -- what follows it only reads the text;
+    // counted: each level with its own counts, and the status launches read the head of the sums, so their event goes last
+    ret = launch_csv_lzmh(ctx, sums.a[k], C, dega_hip_aggregate_rows(T, num_values[k]), ld, decimals, column, separator_char, t, text_stride[k], out[k], cap[k],
+                          out_bits[k], text_len != nullptr ? text_len[k] : nullptr, err[k], s, &rendered,
+                          count == nullptr && k + 1 == K ? ctx->sums.done : nullptr, count != nullptr ? out_count[k] : nullptr);
+    if (count != nullptr && ret == DEGA_OK)
+      ret = launch_status(ctx, first, C, err[k], out_bits[k], s);
   }
-  // (recorded whatever the launches said.  When all went well the sums' event is already on the stream, behind the last
-  // renderer -- their last reader; what follows it only reads the text)
-  if (ret != DEGA_OK)
-    HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
-  ctx->agg_stream = s;
-  ctx->agg_pending = true;
-  if (rendered)
-  {
-    HIP_TRY(ctx, hipEventRecord(ctx->txt_done, s), DEGA_ERROR_LIBRARY_CALL);
-    ctx->txt_stream = s;
-    ctx->txt_pending = true;
-  }
-  return ret;
+  // (recorded whatever the launches said; uniform, when all went well, the sums' event is already on the stream)
+  int rel = scratch_release(ctx, ctx->sums, s, count == nullptr && ret == DEGA_OK);
+  if (rel == DEGA_OK && rendered)
+    rel = scratch_release(ctx, ctx->text, s);
+  return rel != DEGA_OK ? rel : ret;
+}
+
+extern "C" int dega_hip_lzmh_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const size_t *num_values, size_t K,
+                                                   unsigned decimals, size_t column, int separator_char, const size_t *text_stride, uint8_t *const *out,
+                                                   const size_t *cap, uint64_t *const *out_bits, uint64_t *const *text_len, int32_t *const *err,
+                                                   void *stream)
+{
+  return lzmh_encode_levels(ctx, v_tc, C, T, ld, false, nullptr, num_values, K, decimals, column, separator_char, text_stride, out, cap, out_bits, text_len,
+                            nullptr, err, (hipStream_t)stream);
 }
 
 extern "C" int dega_hip_lzmh_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
@@ -1853,90 +1790,8 @@ extern "C" int dega_hip_lzmh_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const 
                                                        const size_t *text_stride, uint8_t *const *out, const size_t *cap, uint64_t *const *out_bits,
                                                        uint64_t *const *text_len, uint64_t *const *out_count, int32_t *const *err, void *stream)
 {
-  if (ctx == nullptr)
-    return DEGA_ERROR_INVALID_VALUE;
-  if (check_level_list(num_values, K) != DEGA_OK)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: at most 8 levels, every num_values at least 1, none twice", hipSuccess);
-  if (K == 0)
-    return DEGA_OK;
-  if (text_stride == nullptr || out == nullptr || cap == nullptr || out_bits == nullptr || err == nullptr || out_count == nullptr)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: text_stride, out, cap, out_bits, out_count and err are arrays of K entries", hipSuccess);
-  int ret;
-  size_t rows[AGG_MAX_LEVELS], off[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, widest = 0;
-  for (size_t k = 0; k < K; k++) // every level judged before the first launch, as in the uniform call
-  {
-    if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, text_stride[k])) != DEGA_OK)
-      return ret;
-    if ((ret = check_lzmh_outputs(ctx, C, out[k], cap[k], out_bits[k], err[k])) != DEGA_OK)
-      return ret;
-    for (size_t i = 0; i < k; i++)
-      if (ranges_overlap(out[k], C * cap[k], out[i], C * cap[i]))
-        return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: two levels' outputs overlap", hipSuccess);
-    rows[k] = dega_hip_aggregate_rows(T, num_values[k]);
-    off[k] = floats;
-    ldo[k] = ld;
-    floats += round4(rows[k] * ld);
-    widest = std::max(widest, text_stride[k]);
-  }
-  if (C == 0)
-    return DEGA_OK;
-  if ((ret = check_counts(ctx, C, T, count, out_count, K, err[0])) != DEGA_OK)
-    return ret;
-  for (size_t k = 0; k < K; k++)
-    if (((uintptr_t)err[k] & 3u) != 0 || ((uintptr_t)out_bits[k] & 7u) != 0)
-      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: misaligned output", hipSuccess);
-  if (T != 0 && (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0))
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: v_tc must be a float32 device array", hipSuccess);
-  for (size_t k = 0; k < K && T != 0; k++)
-    if (ranges_overlap(out[k], C * cap[k], v_tc, ((T - 1) * ld + C) * sizeof(float)))
-      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode levels: an output overlaps v_tc", hipSuccess);
-  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t head = round4(C); // the aggregate pass's status (a count above T) in front of the sums
-  if ((ret = agg_scratch_need(ctx, head + std::max<size_t>(floats, 4))) != DEGA_OK)
-    return ret;
-  int32_t *const first = (int32_t *)ctx->agg_scratch;
-  float *a[AGG_MAX_LEVELS];
-  for (size_t k = 0; k < K; k++)
-    a[k] = ctx->agg_scratch + head + off[k];
-  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, num_values, K, a, ldo)) != DEGA_OK)
-    return ret;
-  TextScratch t;
-  if ((ret = txt_scratch_need(ctx, C, widest, t)) != DEGA_OK)
-    return ret;
-  if (ctx->agg_done == nullptr)
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->agg_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
-  if (ctx->txt_done == nullptr)
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txt_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
-  if (ctx->agg_pending && ctx->agg_stream != s)
-    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->agg_done, 0), DEGA_ERROR_LIBRARY_CALL);
-  if (ctx->txt_pending && ctx->txt_stream != s)
-    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->txt_done, 0), DEGA_ERROR_LIBRARY_CALL);
-  bool rendered = false;
-  ret = launch_aggregate_levels_var(ctx, v_tc, C, T, ld, count, num_values, K, a, ldo, out_count, first, s);
-  for (size_t k = 0; k < K && ret == DEGA_OK; k++)
-  {
-    // every level through the aggregate stage, num_values 1 included, with that level's own counts
-    ret = launch_csv_lzmh(ctx, a[k], C, rows[k], ld, decimals, column, separator_char, t, text_stride[k], out[k], cap[k], out_bits[k],
-                          text_len != nullptr ? text_len[k] : nullptr, err[k], s, &rendered, nullptr, out_count[k]);
-    if (ret == DEGA_OK)
-    {
-      hipLaunchKernelGGL(dega_first_status_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, first, C, err[k], out_bits[k]);
-      if (hipGetLastError() != hipSuccess)
-        ret = fail(ctx, DEGA_ERROR_LIBRARY_CALL, "hipLaunchKernel", hipSuccess);
-    }
-  }
-  // (recorded whatever the launches said; the status launches read the aggregate scratch's head, so its event goes last)
-  HIP_TRY(ctx, hipEventRecord(ctx->agg_done, s), DEGA_ERROR_LIBRARY_CALL);
-  ctx->agg_stream = s;
-  ctx->agg_pending = true;
-  if (rendered)
-  {
-    HIP_TRY(ctx, hipEventRecord(ctx->txt_done, s), DEGA_ERROR_LIBRARY_CALL);
-    ctx->txt_stream = s;
-    ctx->txt_pending = true;
-  }
-  return ret;
+  return lzmh_encode_levels(ctx, v_tc, C, T, ld, true, count, num_values, K, decimals, column, separator_char, text_stride, out, cap, out_bits, text_len,
+                            out_count, err, (hipStream_t)stream);
 }
 
 // ---- decode csv (DCLib/src/csv.c:13-44): text as float32 series, alone and behind LZMH ------------------------------------
@@ -1981,7 +1836,7 @@ static int check_csv_read_outputs(dega_hip_ctx *ctx, const float *v_tc, size_t m
 {
   if (out_count == nullptr || err == nullptr || ((uintptr_t)out_count & 7u) != 0 || ((uintptr_t)err & 3u) != 0)
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: out_count and err must be arrays", hipSuccess);
-  if (max_T != 0 && (v_tc == nullptr || ((uintptr_t)v_tc & 3u) != 0))
+  if (max_T != 0 && !f32_array(v_tc))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: v_tc must be a float32 array", hipSuccess);
   return DEGA_OK;
 }
@@ -2002,21 +1857,10 @@ extern "C" int dega_hip_csv_read_dev(dega_hip_ctx *ctx, const uint8_t *text, siz
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: text and len must be device arrays", hipSuccess);
   if ((ret = check_csv_read_outputs(ctx, v_tc, max_T, out_count, err)) != DEGA_OK)
     return ret;
-  if (max_T != 0 && ranges_overlap(text, C * stride, v_tc, ((max_T - 1) * ld + C) * sizeof(float)))
+  if (max_T != 0 && ranges_overlap(text, C * stride, v_tc, image_bytes(max_T, ld, C)))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: v_tc overlaps text", hipSuccess);
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
   return launch_csv_read(ctx, text, stride, len, C, column, separator_char, v_tc, max_T, ld, out_count, err, (hipStream_t)stream);
-}
-
-// A channel whose text did not fit its row was read as the empty text: it reports the LZMH decoder's status and no value.
-__global__ void __launch_bounds__(256) dega_csv_read_status_kernel(const int32_t *lzmh_err, size_t C, int32_t *err, uint64_t *out_count)
-{
-  const size_t c = (size_t)blockIdx.x * 256u + threadIdx.x;
-  if (c < C && lzmh_err[c] != 0)
-  {
-    err[c] = lzmh_err[c];
-    out_count[c] = 0;
-  }
 }
 
 extern "C" int dega_hip_lzmh_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t text_stride,
@@ -2036,34 +1880,24 @@ extern "C" int dega_hip_lzmh_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh decode: in and in_bits must be device arrays", hipSuccess);
   if ((ret = check_csv_read_outputs(ctx, v_tc, max_T, out_count, err)) != DEGA_OK)
     return ret;
-  if (max_T != 0 && ranges_overlap(in, C * cap, v_tc, ((max_T - 1) * ld + C) * sizeof(float)))
+  if (max_T != 0 && ranges_overlap(in, C * cap, v_tc, image_bytes(max_T, ld, C)))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh decode: v_tc overlaps in", hipSuccess);
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
   hipStream_t s = (hipStream_t)stream;
   TextScratch t;
-  if ((ret = txt_scratch_need(ctx, C, text_stride, t)) != DEGA_OK)
+  if ((ret = text_scratch_acquire(ctx, C, text_stride, s, t)) != DEGA_OK)
     return ret;
-  if (ctx->txt_done == nullptr)
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->txt_done, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
-  // the text scratch may still be in use by an earlier call on another stream: this stream goes on behind it
-  if (ctx->txt_pending && ctx->txt_stream != s)
-    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->txt_done, 0), DEGA_ERROR_LIBRARY_CALL);
   uint64_t *const len = text_len != nullptr ? text_len : t.len;
   // (t.csv_err holds the LZMH decoder's status here)
   ret = dega_hip_lzmh_decode_dev(ctx, in, cap, in_bits, C, t.text, text_stride, len, t.csv_err, s);
   if (ret == DEGA_OK)
     ret = launch_csv_read(ctx, t.text, text_stride, len, C, column, separator_char, v_tc, max_T, ld, out_count, err, s);
+  // A channel whose text did not fit its row was read as the empty text: it reports the LZMH decoder's status and no value.
   if (ret == DEGA_OK)
-  {
-    hipLaunchKernelGGL(dega_csv_read_status_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, t.csv_err, C, err, out_count);
-    if (hipGetLastError() != hipSuccess)
-      ret = fail(ctx, DEGA_ERROR_LIBRARY_CALL, "hipLaunchKernel", hipSuccess);
-  }
+    ret = launch_status(ctx, t.csv_err, C, err, out_count, s);
   // (recorded whatever the launches said: the decoder may be on the stream and writes the scratch)
-  HIP_TRY(ctx, hipEventRecord(ctx->txt_done, s), DEGA_ERROR_LIBRARY_CALL);
-  ctx->txt_stream = s;
-  ctx->txt_pending = true;
-  return ret;
+  const int rel = scratch_release(ctx, ctx->text, s);
+  return rel != DEGA_OK ? rel : ret;
 }
 
 // ---- host-pointer entry points: the pipeline and the multi-device group ------------------------------------------------------

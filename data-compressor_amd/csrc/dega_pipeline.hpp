@@ -1051,29 +1051,19 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &job, const size_t
     else
       HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, src, j.ld * esz, n * esz, j.T, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
     // the sums of the summed levels: the plan's passes over the chunk's image (pitch n), every level 16-byte aligned
-    size_t N[AGG_MAX_LEVELS], ldo[AGG_MAX_LEVELS], floats = 0, m = 0;
-    float *a[AGG_MAX_LEVELS];
-    for (size_t k = 0; k < K; k++)
+    LevelSums sums(num_values, K, j.T, n, false);
+    sums.place((float *)sl.a.p);
+    for (size_t k = 0, m = 0; k < K; k++)
     {
       EncChunk &e = ch.lv[k];
       e.n = n;
       e.rows_ld = n;
       e.redone = false;
       e.total = 0;
-      if (num_values[k] == 1)
-      {
-        e.rows = (const uint8_t *)sl.c.p;
-        continue;
-      }
-      N[m] = num_values[k];
-      a[m] = (float *)sl.a.p + floats;
-      ldo[m] = n;
-      e.rows = (const uint8_t *)a[m];
-      floats += (lj[k].T * n + 3) & ~(size_t)3;
-      m++;
+      e.rows = num_values[k] == 1 ? (const uint8_t *)sl.c.p : (const uint8_t *)sums.a[m++];
     }
-    if ((r = check_levels_dev(ctx, (const float *)sl.c.p, n, j.T, n, N, m, a, ldo)) != DEGA_OK ||
-        (r = launch_aggregate_levels(ctx, (const float *)sl.c.p, n, j.T, n, N, m, a, ldo, sl.s)) != DEGA_OK)
+    if ((r = check_levels_dev(ctx, (const float *)sl.c.p, n, j.T, n, sums.N, sums.n, sums.a, sums.ldo)) != DEGA_OK ||
+        (r = launch_aggregate_levels(ctx, (const float *)sl.c.p, n, j.T, n, nullptr, sums.N, sums.n, sums.a, sums.ldo, nullptr, nullptr, sl.s)) != DEGA_OK)
       return r;
     size_t slab_off = 0;
     for (size_t k = 0; k < K; k++)

@@ -278,6 +278,52 @@ def test_all_counts_equal_T_is_the_uniform_call(ctx):
         assert all((host(p) == host(q)).all() for p, q in zip(x[:4], y))
 
 
+def test_uniform_and_counted_calls_on_two_streams_share_the_scratches(ctx):
+    """a uniform and a counted level call on one context, back to back on different streams without a synchronisation in
+    between, in both orders: the two lay the sums block out differently (the counted call keeps per-channel statuses where
+    the uniform call keeps its first level's sums), and every result equals that of the same call made alone"""
+    import torch
+    rng = np.random.default_rng(91)
+    T, Cn, bad = 2000, 1024, 517
+    va, vb = dev(meter(rng, T, Cn, top=30.0)), dev(meter(rng, T, Cn, top=3000.0))
+    count = rng.integers(0, T + 1, Cn).astype(np.int64)
+    count[bad] = T + 1
+    cb = dev(count)
+    levels = [1, 7]
+    stride = T * 9 + 16
+    pairs = {
+        "dega": (lambda: ctx.encode_f32_levels(va, levels), lambda: ctx.encode_f32_levels(vb, levels, count=cb), 2),
+        "lzmh": (lambda: ctx.lzmh_encode_levels_f32(va, levels, stride), lambda: ctx.lzmh_encode_levels_f32(vb, levels, stride, count=cb), 3),
+    }
+
+    def same(got, want):  # per level (out, bits, ..., err[, counts]): the streams as far as the longest goes, the rest in full
+        for g, w in zip(got, want):
+            nbytes = (int(w[1].max()) + 7) // 8
+            if not (len(g) == len(w) and torch.equal(g[0][:, :nbytes], w[0][:, :nbytes]) and all(torch.equal(x, y) for x, y in zip(g[1:], w[1:]))):
+                return False
+        return len(got) == len(want)
+
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    for name, (uniform, counted, status) in pairs.items():
+        alone = []
+        for call in (uniform, counted):
+            res = call()
+            torch.cuda.synchronize()
+            alone.append([[t.clone() for t in level] for level in res])
+        for lu, lc in zip(*alone):
+            assert not torch.equal(lu[1], lc[1]), name  # (a mix-up of the two batches would show)
+            assert (lu[status] == 0).all(), name
+            assert int(lc[status][bad]) == INVALID and int(lc[1][bad]) == 0, name
+        for first, second in ((0, 1), (1, 0)):
+            torch.cuda.synchronize()
+            with torch.cuda.stream(s1):
+                r1 = (uniform, counted)[first]()
+            with torch.cuda.stream(s2):
+                r2 = (uniform, counted)[second]()
+            torch.cuda.synchronize()
+            assert same(r1, alone[first]) and same(r2, alone[second]), (name, first)
+
+
 # ---- refusals --------------------------------------------------------------------------------------------------------------------
 
 def test_refusals_launch_nothing(dca, ctx):
