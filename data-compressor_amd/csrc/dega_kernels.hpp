@@ -71,7 +71,11 @@ static_assert(ENC_FILL_WORDS < ENC_RING, "ring too small");
 
 // A channel can be coded over several launches, each taking the next range of rows (the host pipeline uploads a batch of
 // few, long channels in bands and codes every band as it lands; a stream longer than one call's 2^25 samples): the state
-// of a lane's three state machines between two launches, ENC_STATE_WORDS dwords per channel, [word][channel].
+// of a lane's three state machines between two launches, ENC_STATE_WORDS dwords per channel, [word][channel]:
+//   0..5   the filler: bit queue (acc low, acc high, cnt), last sample (low, high), its verdict
+//   6..10  the writer: F (low, high), fcnt, the held-back word, pos
+//   11..15 the coder: the interval (A, B), the model (c1, tot, mps)
+//   16, 17 the writer again: err, lost_ones (BacWriter: the all-ones words dropped last beyond a short slab's end)
 constexpr uint32_t ENC_STATE_WORDS = 18;
 constexpr uint32_t ENC_SEG_CONTINUES = 1; // the launch goes on from saved state
 constexpr uint32_t ENC_SEG_MORE = 2;      // more rows follow in a later launch: no EOF symbol, state saved
@@ -221,6 +225,7 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
     last64 = ((uint64_t)state[4 * a.C] << 32) | last;
     lane_err = (int32_t)state[5 * a.C];
     wr.err = (int32_t)state[16 * a.C];
+    wr.lost_ones = state[17 * a.C];
     wr.F = ((uint64_t)state[7 * a.C] << 32) | state[6 * a.C];
     wr.fcnt = state[8 * a.C];
     wr.prev = state[9 * a.C];
@@ -564,6 +569,7 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
       state[9 * a.C] = wr.prev;
       state[10 * a.C] = wr.pos;
       state[16 * a.C] = (uint32_t)wr.err;
+      state[17 * a.C] = wr.lost_ones;
     }
   }
   else

@@ -483,6 +483,7 @@ struct BacWriter
   uint32_t prev, pos;       // pos = words completed so far; prev is word pos-1 (held back)
   uint32_t drained, staged; // words [0, drained) are in the slab, [drained, drained + staged) in the lane's LDS column
   uint32_t cap_words;
+  uint32_t lost_ones; // words beyond the slab's end that were dropped last and were all ones, in a row (see ripple_carry_from)
   uint32_t *dst;   // channel's slab (global memory)
   uint32_t *oring; // lane's column of the LDS staging ring: word w at oring[(w % ORING) * 64]
   int32_t err;
@@ -496,6 +497,7 @@ struct BacWriter
     drained = 0;
     staged = 0;
     cap_words = cap_words_;
+    lost_ones = 0;
     dst = dst_;
     oring = oring_;
     err = OK;
@@ -505,8 +507,11 @@ struct BacWriter
   {
     if (index < cap_words)
       dst[index] = bswap32(word); // MSB-first bit order => big-endian words
-    else if (err == OK)
+    else
+    {
       err = ERR_MEMORY;
+      lost_ones = word == 0xFFFFFFFFu ? lost_ones + 1u : 0u;
+    }
   }
 
   DG_DEV void drain_lane() // LDS column -> slab, this lane only (the kernel normally drains whole waves in lockstep)
@@ -541,20 +546,36 @@ struct BacWriter
     staged++;
   }
 
-  // add one to the big number formed by words [0, count): the staged ones first, then the slab (rare: a carry past `prev`)
+  // add one to the big number formed by words [0, count): the staged ones first, then the slab (rare: a carry past `prev`
+  // -- once in 2^32 hand-overs of random data; tests/encoder_regimes_common.py steers series that bring it about several
+  // times per channel, after hundreds of owed bits).  Words at and beyond cap_words were dropped, not stored: the carry
+  // runs through them into the slab only if every one of them was all ones, which put_word has counted.  However the
+  // carry ends, none comes this far down again (the stream so far is a number that the coder's interval lets grow by less
+  // than one unit of word count - 1: a second carry would make it two), so the count starts anew.  Only the words below
+  // `count` are drained: a caller may have staged word `count` itself already (absorb4_in_step).
   DG_DEV void ripple_carry_from(uint32_t count)
   {
-    drain_lane();
+    while (drained < count)
+    {
+      put_word(drained, oring[(drained % ORING) * 64u]);
+      drained++;
+      staged--;
+    }
+    if (count > cap_words)
+    {
+      const bool through = lost_ones >= count - cap_words;
+      lost_ones = 0;
+      if (!through)
+        return;
+      count = cap_words;
+    }
     while (count > 0)
     {
       --count;
-      if (count < cap_words)
-      {
-        const uint32_t w = bswap32(dst[count]) + 1u;
-        dst[count] = bswap32(w);
-        if (w != 0)
-          break;
-      }
+      const uint32_t w = bswap32(dst[count]) + 1u;
+      dst[count] = bswap32(w);
+      if (w != 0)
+        break;
     }
   }
 
@@ -612,8 +633,8 @@ struct BacWriter
 
   // The same for a whole wave in step, branch free: fits4(), a word held back already (pos >= 1) and room in the staging
   // column are the caller's business.  Returns true when a carry ran past the held-back word (it was all ones: once in
-  // 2^32 hand-overs of random data): the caller then calls ripple_carry_from(pos - 2) -- the word just staged is word
-  // pos - 2, the carry belongs in the words in front of it.
+  // 2^32 hand-overs of random data, see ripple_carry_from): the caller then calls ripple_carry_from(pos - 2) -- the word
+  // just staged is word pos - 2, the carry belongs in the words in front of it.
   DG_DEV bool absorb4_in_step(const uint32_t (&hi)[4])
   {
 #pragma unroll
