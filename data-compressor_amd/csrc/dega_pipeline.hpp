@@ -607,16 +607,108 @@ static size_t band_rows_of(const ChunkPlan &plan, const Shape &j, size_t row_byt
 
 // ---- encode ------------------------------------------------------------------------------------------------------------
 
-struct EncodeSink
+// The packed outputs of a call (of one device's share of it; of one level), every codec's: streams back to back
+struct PackedOut
 {
-  uint8_t *packed = nullptr; // packed mode: streams back to back ...
+  uint8_t *packed = nullptr;
   size_t packed_cap = 0;
-  uint64_t *offsets = nullptr; // ... channel c at packed[offsets[c] .. offsets[c+1]); C + 1 entries
-  uint8_t *slabs = nullptr;    // slab mode: channel c at slabs + c * slab_cap
-  size_t slab_cap = 0;
+  uint64_t *offsets = nullptr; // channel c at packed[offsets[c] .. offsets[c+1]); C + 1 entries, relative to the share
   uint64_t *bits = nullptr;
   int32_t *err = nullptr;
+  uint64_t total = 0; // out: packed bytes of the chunks handed out so far, in the end of the share (the size needed when full)
+  bool full = false;  // out: packed_cap was too small; the share was sized, not delivered (means nothing where no buffer was given)
 };
+
+static PackedOut packed_out(uint8_t *packed, size_t packed_cap, uint64_t *offsets, uint64_t *bits, int32_t *err)
+{
+  PackedOut out;
+  out.packed = packed;
+  out.packed_cap = packed_cap;
+  out.offsets = offsets;
+  out.bits = bits;
+  out.err = err;
+  return out;
+}
+
+struct EncodeSink : PackedOut // the plain encoder's: packed mode, or
+{
+  uint8_t *slabs = nullptr; // slab mode: channel c at slabs + c * slab_cap
+  size_t slab_cap = 0;
+};
+
+static Shape chunk_shape(const Shape &j, size_t n) // n channels of a batch as a time-major image of their own on the device
+{
+  Shape cj = j;
+  cj.C = n;
+  cj.ld = n;
+  return cj;
+}
+
+// ---- the encode tail, every codec's: from the bit lengths of a chunk's streams on the device to their bytes on the host ----
+
+// Sizes on their way home: the streams' offsets from their bit lengths (dm), and -- where the chunk has one set of the
+// small arrays -- the set into its pinned mirror
+static int sizes_home(dega_hip_ctx *ctx, hipStream_t s, const MetaView &dm, size_t n, void *mirror)
+{
+  hipLaunchKernelGGL(dega_offsets_kernel, dim3(1), dim3(1024), 0, s, dm.bits, n, dm.offsets);
+  HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+  if (mirror != nullptr)
+    HIP_TRY(ctx, hipMemcpyAsync(mirror, dm.bits, MetaView::bytes(n), hipMemcpyDeviceToHost, s), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
+// n streams between their slabs (channel i at slabs + i * cap) and back to back at `packed`, by offsets[n + 1] on the device
+static int launch_gather(dega_hip_ctx *ctx, hipStream_t s, const void *slabs, size_t cap, const uint64_t *offsets, size_t n, void *packed, bool scatter = false)
+{
+  GatherArgs g{(const uint8_t *)slabs, cap, offsets, n, (uint8_t *)packed};
+  if (scatter)
+    hipLaunchKernelGGL(dega_scatter_kernel, dim3((unsigned)((n + WAVES - 1) / WAVES)), dim3(BLOCK), 0, s, g);
+  else
+    hipLaunchKernelGGL(dega_gather_kernel, dim3((unsigned)((n + WAVES - 1) / WAVES)), dim3(BLOCK), 0, s, g);
+  HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+static int launch_scatter(dega_hip_ctx *ctx, hipStream_t s, void *slabs, size_t cap, const uint64_t *offsets, size_t n, const void *packed)
+{
+  return launch_gather(ctx, s, slabs, cap, offsets, n, const_cast<void *>(packed), true);
+}
+
+// Chunk out, the host's half: the sizes of channels [c0, c0 + n) are on the host (hm, offsets relative to the chunk).  Hands
+// out bits / err / offsets at the running total; true when the chunk's bytes are to go to out.packed + base now -- there are
+// some, and they and everything before them fit (after the first chunk that does not, the rest is only sized: the caller
+// learns what it needs).
+static bool chunk_sized(PackedOut &out, size_t c0, size_t n, const MetaView &hm, uint64_t &base)
+{
+  base = out.total;
+  for (size_t i = 0; i < n; i++)
+  {
+    out.bits[c0 + i] = hm.bits[i];
+    out.err[c0 + i] = hm.err[i];
+  }
+  if (out.offsets != nullptr)
+    for (size_t i = 0; i < n; i++)
+      out.offsets[c0 + i] = base + hm.offsets[i];
+  out.total += hm.offsets[n];
+  out.full = out.full || out.total > out.packed_cap;
+  return !out.full && hm.offsets[n] > 0;
+}
+
+// Chunk out, the device's half: the chunk's `total` bytes are gathered from (slabs, cap) into dev -- a buffer of the slot
+// that is free by now -- and sent to dst; the bytes of a chunk that was redone are on the host already (redo) and copied.
+static int chunk_home(dega_hip_ctx *ctx, Pipeline *pl, hipStream_t s, uint8_t *dst, bool dst_pinned, size_t total, const std::vector<uint8_t> *redo,
+                      const void *slabs, size_t cap, const uint64_t *dev_offsets, size_t n, void *dev)
+{
+  if (redo != nullptr)
+  {
+    memcpy(dst, redo->data(), total);
+    return DEGA_OK;
+  }
+  const int ret = launch_gather(ctx, s, slabs, cap, dev_offsets, n, dev);
+  if (ret != DEGA_OK)
+    return ret;
+  HIP_TRY(ctx, rows_to_host(pl, s, dst, total, dev, total, 1, dst_pinned), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
 
 struct EncChunk : Chunk
 {
@@ -631,7 +723,6 @@ struct EncChunk : Chunk
 struct EncodeRun // state of one device's share of a batch between the two phases of a group call
 {
   std::vector<EncChunk> chunks;
-  uint64_t total = 0;
 };
 
 // the worst-case pass over one chunk, a few channels at a time, synchronous: rare (streams longer than their samples)
@@ -654,15 +745,15 @@ static int encode_redo_chunk(dega_hip_ctx *ctx, Pipeline *pl, Slot &sl, const Sh
     int ret;
     if ((ret = launch_encode(ctx, ch.rows + j0 * sample_bytes(cj), sj, batch_C, (uint8_t *)pl->redo_slabs.p, wc, dm.bits, dm.err, sl.s)) != DEGA_OK)
       return ret;
-    hipLaunchKernelGGL(dega_offsets_kernel, dim3(1), dim3(1024), 0, sl.s, dm.bits, n, dm.offsets);
-    HIP_TRY(ctx, hipMemcpyAsync(pl->redo_hmeta.p, pl->redo_meta.p, MetaView::bytes(n), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    if ((ret = sizes_home(ctx, sl.s, dm, n, pl->redo_hmeta.p)) != DEGA_OK)
+      return ret;
     HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
     const uint64_t tot = rm.offsets[n];
     HIP_TRY(ctx, pl->redo_packed.need((size_t)tot + 16), DEGA_ERROR_MEMORY);
     if (tot > 0)
     {
-      GatherArgs g{(const uint8_t *)pl->redo_slabs.p, wc, dm.offsets, n, (uint8_t *)pl->redo_packed.p};
-      hipLaunchKernelGGL(dega_gather_kernel, dim3((unsigned)((n + WAVES - 1) / WAVES)), dim3(BLOCK), 0, sl.s, g);
+      if ((ret = launch_gather(ctx, sl.s, pl->redo_slabs.p, wc, dm.offsets, n, pl->redo_packed.p)) != DEGA_OK)
+        return ret;
       ch.redo_bytes.resize((size_t)(running + tot));
       HIP_TRY(ctx, hipMemcpyAsync(ch.redo_bytes.data() + running, pl->redo_packed.p, (size_t)tot, hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
       HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
@@ -716,7 +807,7 @@ static bool read_in_place()
 // Phase A of one device's share: channels [0, j.C) of `samples` (host, row pitch j.ld).  Uploads, codes and sizes every
 // chunk; with `deliver` the packed bytes of each chunk also go out at once (base = running total); without, they stay
 // on the device (gathered) for encode_deliver().  bits / err / offsets (relative to this share) are final on return.
-static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples, const EncodeSink &sink, bool deliver, EncodeRun &run)
+static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples, EncodeSink &sink, bool deliver, EncodeRun &run)
 {
   // Channel-major samples ([C][ld], ld >= T): a chunk's channels go up as they lie -- n rows of T samples, one contiguous
   // copy when ld == T -- into the slot's SLAB buffer, which is free until the chunk's encode launch writes it (everything
@@ -739,8 +830,8 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
   if (plan.nslots < 0)
     return fail(ctx, DEGA_ERROR_MEMORY, "the device's share of the batch does not fit its memory", hipSuccess);
   run.chunks.assign(plan.nchunks, EncChunk());
-  run.total = 0;
-  bool out_full = false;
+  sink.total = 0;
+  sink.full = false;
   const bool samples_pinned = is_pinned(samples), packed_pinned = is_pinned(sink.packed);
   const bool in_place = samples_pinned && read_in_place() && !cmajor;
 
@@ -758,9 +849,7 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
     HIP_TRY(ctx, sl.meta.need(MetaView::bytes(ch.n)), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.hmeta.need(MetaView::bytes(ch.n)), DEGA_ERROR_MEMORY);
     MetaView dm(sl.meta.p, ch.n);
-    Shape cj = j;
-    cj.C = ch.n;
-    cj.ld = ch.n;
+    Shape cj = chunk_shape(j, ch.n);
     const uint8_t *const src = (const uint8_t *)samples + ch.c0 * (cmajor ? j.ld : 1) * esz;
     const size_t band_rows = cmajor ? 0 : band_rows_of(plan, j, ch.n * esz);
     ch.rows = (const uint8_t *)sl.a.p;
@@ -837,9 +926,8 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
       TRACE("chunk %zu: %zu bands of %zu rows, one launch each", k, nbands, band_rows);
       ch.bands = true;
     }
-    hipLaunchKernelGGL(dega_offsets_kernel, dim3(1), dim3(1024), 0, sl.s, dm.bits, ch.n, dm.offsets);
-    HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, hipMemcpyAsync(sl.hmeta.p, sl.meta.p, MetaView::bytes(ch.n), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    if ((r = sizes_home(ctx, sl.s, dm, ch.n, sl.hmeta.p)) != DEGA_OK)
+      return r;
     TRACE("chunk %zu stage1 enqueued", k);
     return DEGA_OK;
   };
@@ -856,67 +944,41 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
     if (cap < worst_cap(j))
       for (size_t i = 0; i < ch.n && !too_small; i++)
         too_small = hm.err[i] == DEGA_ERROR_MEMORY;
-    Shape cj = j;
-    cj.C = ch.n;
-    cj.ld = ch.n;
     int r;
-    if (too_small && (r = encode_redo_chunk(ctx, pl, sl, cj, j.C, ch, hm)) != DEGA_OK)
+    if (too_small && (r = encode_redo_chunk(ctx, pl, sl, chunk_shape(j, ch.n), j.C, ch, hm)) != DEGA_OK)
       return r;
     ch.total = hm.offsets[ch.n];
-    const uint64_t base = run.total;
+    uint64_t base;
+    const bool fits = chunk_sized(sink, ch.c0, ch.n, hm, base);
+    ch.gathered = true;
+    // the samples are no longer needed: their buffer takes the packed streams (it holds max(samples, slabs) bytes)
+    if (deliver && sink.slabs == nullptr) // packed mode: the streams go home at once
+      return !fits ? DEGA_OK
+                   : chunk_home(ctx, pl, sl.s, sink.packed + base, packed_pinned, (size_t)ch.total, ch.redone ? &ch.redo_bytes : nullptr, sl.b.p, cap, dm.offsets,
+                                ch.n, sl.a.p);
+    if (!ch.redone && ch.total > 0 && (r = launch_gather(ctx, sl.s, sl.b.p, cap, dm.offsets, ch.n, sl.a.p)) != DEGA_OK)
+      return r;
+    if (!deliver) // the streams stay where they are for encode_deliver()
+      return DEGA_OK;
+    // slab mode: through the pinned stage, then channel by channel to its slab
+    const uint8_t *srcb = nullptr;
+    if (ch.redone)
+      srcb = ch.redo_bytes.data();
+    else if (ch.total > 0)
+    {
+      HIP_TRY(ctx, sl.stage.need((size_t)ch.total), DEGA_ERROR_MEMORY);
+      HIP_TRY(ctx, hipMemcpyAsync(sl.stage.p, sl.a.p, (size_t)ch.total, hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
+      HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+      srcb = (const uint8_t *)sl.stage.p;
+    }
     for (size_t i = 0; i < ch.n; i++)
     {
-      sink.bits[ch.c0 + i] = hm.bits[i];
-      sink.err[ch.c0 + i] = hm.err[i];
+      const size_t nb = (size_t)(hm.offsets[i + 1] - hm.offsets[i]);
+      if (nb > sink.slab_cap && sink.err[ch.c0 + i] == DEGA_OK)
+        sink.err[ch.c0 + i] = DEGA_ERROR_MEMORY; // the stream does not fit the caller's slab: its head is there, its length is reported
+      if (nb > 0)
+        memcpy(sink.slabs + (ch.c0 + i) * sink.slab_cap, srcb + hm.offsets[i], std::min(nb, sink.slab_cap));
     }
-    if (sink.offsets != nullptr)
-      for (size_t i = 0; i < ch.n; i++)
-        sink.offsets[ch.c0 + i] = base + hm.offsets[i];
-    run.total += ch.total;
-    if (!ch.redone && ch.total > 0)
-    {
-      // the samples are no longer needed: their buffer takes the packed streams (it holds max(samples, slabs) bytes)
-      GatherArgs g{(const uint8_t *)sl.b.p, cap, dm.offsets, ch.n, (uint8_t *)sl.a.p};
-      hipLaunchKernelGGL(dega_gather_kernel, dim3((unsigned)((ch.n + WAVES - 1) / WAVES)), dim3(BLOCK), 0, sl.s, g);
-      HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
-    }
-    ch.gathered = true;
-    if (!deliver)
-      return DEGA_OK;
-    if (sink.slabs != nullptr)
-    {
-      // slab mode: through the pinned stage, then channel by channel to its slab
-      const uint8_t *srcb = nullptr;
-      if (ch.redone)
-        srcb = ch.redo_bytes.data();
-      else if (ch.total > 0)
-      {
-        HIP_TRY(ctx, sl.stage.need((size_t)ch.total), DEGA_ERROR_MEMORY);
-        HIP_TRY(ctx, hipMemcpyAsync(sl.stage.p, sl.a.p, (size_t)ch.total, hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
-        HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-        srcb = (const uint8_t *)sl.stage.p;
-      }
-      for (size_t i = 0; i < ch.n; i++)
-      {
-        const size_t nb = (size_t)(hm.offsets[i + 1] - hm.offsets[i]);
-        if (nb > sink.slab_cap && sink.err[ch.c0 + i] == DEGA_OK)
-          sink.err[ch.c0 + i] = DEGA_ERROR_MEMORY; // the stream does not fit the caller's slab: its head is there, its length is reported
-        if (nb > 0)
-          memcpy(sink.slabs + (ch.c0 + i) * sink.slab_cap, srcb + hm.offsets[i], std::min(nb, sink.slab_cap));
-      }
-      return DEGA_OK;
-    }
-    if (base + ch.total > sink.packed_cap)
-    {
-      out_full = true; // keep sizing the rest: the caller learns what it needs
-      return DEGA_OK;
-    }
-    if (out_full || ch.total == 0)
-      return DEGA_OK;
-    if (ch.redone)
-      memcpy(sink.packed + base, ch.redo_bytes.data(), (size_t)ch.total);
-    else
-      HIP_TRY(ctx, rows_to_host(pl, sl.s, sink.packed + base, (size_t)ch.total, sl.a.p, (size_t)ch.total, 1, packed_pinned), DEGA_ERROR_LIBRARY_CALL);
     return DEGA_OK;
   };
 
@@ -927,8 +989,8 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
     return ret;
   TRACE("encode share done");
   if (sink.offsets != nullptr)
-    sink.offsets[j.C] = run.total;
-  if (deliver && sink.slabs == nullptr && out_full)
+    sink.offsets[j.C] = sink.total;
+  if (deliver && sink.slabs == nullptr && sink.full)
     return fail(ctx, DEGA_ERROR_MEMORY, "packed buffer too small: offsets[C] holds the size needed", hipSuccess);
   return DEGA_OK;
 }
@@ -959,17 +1021,6 @@ static int encode_deliver(dega_hip_ctx *ctx, EncodeRun &run, uint8_t *packed, ui
 
 // ---- encode, several granularities from one upload (dega_hip_encode_levels_job_host) -------------------------------------------
 
-struct LevelSink // one level's outputs of one device's share
-{
-  uint8_t *packed = nullptr;
-  size_t packed_cap = 0;
-  uint64_t *offsets = nullptr; // C + 1 entries, relative to this share
-  uint64_t *bits = nullptr;
-  int32_t *err = nullptr;
-  uint64_t total = 0; // out: packed bytes of the share (the size needed when full)
-  bool full = false;  // out: packed_cap was too small; the level was sized, not delivered
-};
-
 static size_t meta_stride(size_t n) // the K MetaViews of a slot lie one behind the other, each 8-byte aligned
 {
   return (MetaView::bytes(n) + 7) & ~(size_t)7;
@@ -986,7 +1037,7 @@ static size_t meta_stride(size_t n) // the K MetaViews of a slot lie one behind 
 // j: C, ld, factor, adaptive, valuesize of the job; j.T the FINE length.  Always delivers (no resident phase).
 // `sized`: set once every chunk has been coded and sized, i.e. bits / err / offsets / total of every level are complete;
 // a DEGA_ERROR_MEMORY with `sized` false is a failed allocation, one with `sized` true a packed buffer that is too small.
-static int encode_levels_share(dega_hip_ctx *ctx, const Shape &job, const size_t *num_values, size_t K, const void *samples, LevelSink *sink, bool &sized)
+static int encode_levels_share(dega_hip_ctx *ctx, const Shape &job, const size_t *num_values, size_t K, const void *samples, PackedOut *sink, bool &sized)
 {
   // channel-major samples: as in encode_share, through the slot's slab buffer (free until the first encode launch of the
   // chunk), which then holds max(the levels' slabs, T * esz) bytes per channel
@@ -1069,13 +1120,9 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &job, const size_t
     for (size_t k = 0; k < K; k++)
     {
       MetaView dm((uint8_t *)sl.meta.p + k * meta_stride(n), n);
-      Shape cj = lj[k];
-      cj.C = n;
-      cj.ld = n;
-      if ((r = launch_encode(ctx, ch.lv[k].rows, cj, j.C, (uint8_t *)sl.b.p + slab_off, cap[k], dm.bits, dm.err, sl.s)) != DEGA_OK)
+      if ((r = launch_encode(ctx, ch.lv[k].rows, chunk_shape(lj[k], n), j.C, (uint8_t *)sl.b.p + slab_off, cap[k], dm.bits, dm.err, sl.s)) != DEGA_OK ||
+          (r = sizes_home(ctx, sl.s, dm, n, nullptr)) != DEGA_OK) // (the K sets go home in one copy, below)
         return r;
-      hipLaunchKernelGGL(dega_offsets_kernel, dim3(1), dim3(1024), 0, sl.s, dm.bits, n, dm.offsets);
-      HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
       slab_off += n * cap[k];
     }
     HIP_TRY(ctx, hipMemcpyAsync(sl.hmeta.p, sl.meta.p, K * meta_stride(n), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
@@ -1097,10 +1144,7 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &job, const size_t
       if (cap[k] < worst_cap(lj[k]))
         for (size_t i = 0; i < n && !too_small; i++)
           too_small = hm.err[i] == DEGA_ERROR_MEMORY;
-      Shape cj = lj[k];
-      cj.C = n;
-      cj.ld = n;
-      if (too_small && (r = encode_redo_chunk(ctx, pl, sl, cj, j.C, ch.lv[k], hm)) != DEGA_OK)
+      if (too_small && (r = encode_redo_chunk(ctx, pl, sl, chunk_shape(lj[k], n), j.C, ch.lv[k], hm)) != DEGA_OK)
         return r;
     }
     size_t slab_off = 0, packed_off = 0;
@@ -1108,34 +1152,18 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &job, const size_t
     {
       MetaView hm((uint8_t *)sl.hmeta.p + k * meta_stride(n), n), dm((uint8_t *)sl.meta.p + k * meta_stride(n), n);
       EncChunk &e = ch.lv[k];
-      LevelSink &out = sink[k];
       e.total = hm.offsets[n];
-      const uint64_t base = out.total;
-      for (size_t i = 0; i < n; i++)
-      {
-        out.bits[ch.c0 + i] = hm.bits[i];
-        out.err[ch.c0 + i] = hm.err[i];
-        out.offsets[ch.c0 + i] = base + hm.offsets[i];
-      }
-      out.total += e.total;
       const size_t slabs_at = slab_off;
       slab_off += n * cap[k];
-      if (base + e.total > out.packed_cap)
-        out.full = true; // keep sizing: the caller learns what this level needs
-      if (out.full || e.total == 0)
+      uint64_t base;
+      if (!chunk_sized(sink[k], ch.c0, n, hm, base))
         continue;
-      if (e.redone)
-      {
-        memcpy(out.packed + base, e.redo_bytes.data(), (size_t)e.total);
-        continue;
-      }
       const size_t packed_at = packed_off; // (not redone: at most n * cap[k] bytes, and the buffer holds n * the sum of the caps)
-      packed_off += (size_t)((e.total + 15) & ~(uint64_t)15);
-      GatherArgs g{(const uint8_t *)sl.b.p + slabs_at, cap[k], dm.offsets, n, (uint8_t *)sl.c.p + packed_at};
-      hipLaunchKernelGGL(dega_gather_kernel, dim3((unsigned)((n + WAVES - 1) / WAVES)), dim3(BLOCK), 0, sl.s, g);
-      HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
-      HIP_TRY(ctx, rows_to_host(pl, sl.s, out.packed + base, (size_t)e.total, (uint8_t *)sl.c.p + packed_at, (size_t)e.total, 1, packed_pinned[k]),
-              DEGA_ERROR_LIBRARY_CALL);
+      if (!e.redone)
+        packed_off += (size_t)((e.total + 15) & ~(uint64_t)15);
+      if ((r = chunk_home(ctx, pl, sl.s, sink[k].packed + base, packed_pinned[k], (size_t)e.total, e.redone ? &e.redo_bytes : nullptr,
+                          (const uint8_t *)sl.b.p + slabs_at, cap[k], dm.offsets, n, (uint8_t *)sl.c.p + packed_at)) != DEGA_OK)
+        return r;
     }
     return DEGA_OK;
   };
@@ -1155,6 +1183,35 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &job, const size_t
 }
 
 // ---- decode ------------------------------------------------------------------------------------------------------------
+
+// The decode head, every codec's: the streams of a chunk's n channels -- offsets[0 .. n] into the caller's packed buffer,
+// bits[0 .. n) -- go up on stream `us` and are spread into slabs in the slot's buffer b, one per channel and as long as
+// the chunk's longest stream needs: `cap`, which is returned.  The bit lengths and the offsets, rebased to the chunk, go
+// through the slot's pinned mirror (the caller has waited for the slot's stream: nothing of the slot's is still in use);
+// the packed bytes through its buffer a, which holds at least a_floor bytes.
+static int chunk_in(dega_hip_ctx *ctx, Pipeline *pl, Slot &sl, hipStream_t us, const uint8_t *packed, const uint64_t *offsets, const uint64_t *bits, size_t n,
+                    bool packed_pinned, size_t a_floor, size_t &cap)
+{
+  const uint64_t o0 = offsets[0], nbytes = offsets[n] - o0;
+  uint64_t longest = 0;
+  for (size_t i = 0; i < n; i++)
+    longest = std::max<uint64_t>(longest, offsets[i + 1] - offsets[i]);
+  cap = ((size_t)longest + 16 + 3) & ~(size_t)3; // room for the decoder's word look-ahead
+  HIP_TRY(ctx, sl.a.need(std::max((size_t)nbytes, a_floor) + 64), DEGA_ERROR_MEMORY);
+  HIP_TRY(ctx, sl.b.need(n * cap + 64), DEGA_ERROR_MEMORY);
+  HIP_TRY(ctx, sl.meta.need(MetaView::bytes(n)), DEGA_ERROR_MEMORY);
+  HIP_TRY(ctx, sl.hmeta.need(MetaView::bytes(n)), DEGA_ERROR_MEMORY);
+  MetaView hm(sl.hmeta.p, n), dm(sl.meta.p, n);
+  for (size_t i = 0; i < n; i++)
+  {
+    hm.bits[i] = bits[i];
+    hm.offsets[i] = offsets[i] - o0;
+  }
+  hm.offsets[n] = nbytes;
+  HIP_TRY(ctx, hipMemcpyAsync(sl.meta.p, sl.hmeta.p, (2 * n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, us), DEGA_ERROR_LIBRARY_CALL);
+  HIP_TRY(ctx, rows_to_device(pl, us, sl.a.p, packed + o0, (size_t)nbytes, (size_t)nbytes, 1, packed_pinned), DEGA_ERROR_LIBRARY_CALL);
+  return launch_scatter(ctx, us, sl.b.p, cap, dm.offsets, n, sl.a.p);
+}
 
 static int decode_share(dega_hip_ctx *ctx, const Shape &job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *bits, void *samples,
                         uint64_t *out_count, int32_t *err)
@@ -1203,24 +1260,7 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &job, const uint8_t *pack
     if ((r = slot_stream(ctx, sl)) != DEGA_OK)
       return r;
     HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL); // the pinned mirror is about to be rewritten
-    const uint64_t o0 = offsets[ch.c0], nbytes = offsets[ch.c0 + ch.n] - o0;
-    uint64_t longest = 0;
-    for (size_t i = 0; i < ch.n; i++)
-      longest = std::max<uint64_t>(longest, offsets[ch.c0 + i + 1] - offsets[ch.c0 + i]);
-    const size_t cap = ((size_t)longest + 16 + 3) & ~(size_t)3; // room for the decoder's word look-ahead
-    ch.cap = cap;
-    HIP_TRY(ctx, sl.a.need((cmajor ? std::max<size_t>((size_t)nbytes, ch.n * j.T * osz) : (size_t)nbytes) + 64), DEGA_ERROR_MEMORY);
-    HIP_TRY(ctx, sl.b.need(ch.n * cap + 64), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.c.need(ch.n * j.T * osz + 64), DEGA_ERROR_MEMORY);
-    HIP_TRY(ctx, sl.meta.need(MetaView::bytes(ch.n)), DEGA_ERROR_MEMORY);
-    HIP_TRY(ctx, sl.hmeta.need(MetaView::bytes(ch.n)), DEGA_ERROR_MEMORY);
-    MetaView hm(sl.hmeta.p, ch.n), dm(sl.meta.p, ch.n);
-    for (size_t i = 0; i < ch.n; i++)
-    {
-      hm.bits[i] = bits[ch.c0 + i];
-      hm.offsets[i] = offsets[ch.c0 + i] - o0;
-    }
-    hm.offsets[ch.n] = nbytes;
     // The uploads of all chunks share ONE stream: side by side on their own streams they share the link, every one of
     // them takes as long as all together, and the first kernel starts when the last upload is done (two chunks: 74 ms a
     // call where one chunk takes 66).  The chunk's own stream goes on behind the upload's event.
@@ -1233,13 +1273,8 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &job, const uint8_t *pack
         HIP_TRY(ctx, hipEventCreateWithFlags(&sl.reuse_ev, hipEventDisableTiming), DEGA_ERROR_LIBRARY_CALL);
       us = pl->up;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(sl.meta.p, sl.hmeta.p, (2 * ch.n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, us), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, rows_to_device(pl, us, sl.a.p, packed + o0, (size_t)nbytes, (size_t)nbytes, 1, packed_pinned), DEGA_ERROR_LIBRARY_CALL);
-    {
-      GatherArgs g{(const uint8_t *)sl.b.p, cap, dm.offsets, ch.n, (uint8_t *)sl.a.p};
-      hipLaunchKernelGGL(dega_scatter_kernel, dim3((unsigned)((ch.n + WAVES - 1) / WAVES)), dim3(BLOCK), 0, us, g);
-      HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
-    }
+    if ((r = chunk_in(ctx, pl, sl, us, packed, offsets + ch.c0, bits + ch.c0, ch.n, packed_pinned, cmajor ? ch.n * j.T * osz : 0, ch.cap)) != DEGA_OK)
+      return r;
     if (us != sl.s)
     {
       HIP_TRY(ctx, hipEventRecord(sl.reuse_ev, us), DEGA_ERROR_LIBRARY_CALL);
@@ -1254,9 +1289,7 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &job, const uint8_t *pack
     const size_t cap = ch.cap;
     MetaView hm(sl.hmeta.p, ch.n), dm(sl.meta.p, ch.n);
     int r;
-    Shape cj = j;
-    cj.C = ch.n;
-    cj.ld = ch.n;
+    const Shape cj = chunk_shape(j, ch.n);
     // few, long channels (see encode_share): the rows go home in bands while the kernel is still decoding; every wave of 64
     // channels reports the rows it has stored in a word of pinned host memory
     ch.band_rows = out_count == nullptr && !cmajor ? band_rows_of(plan, j, ch.n * osz) : 0;
@@ -1350,21 +1383,30 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &job, const uint8_t *pack
   return run_chunks(plan.nchunks, std::min<size_t>((size_t)plan.nslots, decode_stages_ahead()), stage1, stage2);
 }
 
+// What is wrong with the packed streams a decode call was given (nullptr: nothing): offsets[C + 1] and bits[C] as the
+// encode calls write them, no stream longer than the codec's decoder takes (`longest`; too_long: what to say of one that is)
+static const char *packed_input_fault(size_t C, const uint64_t *offsets, const uint64_t *bits, uint64_t longest, const char *too_long)
+{
+  static const char *const order = "offsets must grow and hold ceil(bits / 8) bytes per channel";
+  for (size_t c = 0; c < C; c++)
+  {
+    // (bits + 7) / 8 would wrap for lengths near 2^64: compare without the rounding add
+    if (offsets[c + 1] < offsets[c] || bits[c] / 8 > offsets[c + 1] - offsets[c] || (bits[c] / 8 == offsets[c + 1] - offsets[c] && (bits[c] & 7) != 0))
+      return order;
+    if (offsets[c + 1] - offsets[c] > longest)
+      return too_long != nullptr ? too_long : order;
+  }
+  return nullptr;
+}
+
 static int check_packed_input(dega_hip_ctx *ctx, const Shape &j, const uint8_t *packed, const uint64_t *offsets, const uint64_t *bits)
 {
   if (offsets == nullptr || bits == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
   if (j.C > 0 && packed == nullptr && offsets[j.C] != offsets[0])
     return DEGA_ERROR_INVALID_VALUE;
-  for (size_t c = 0; c < j.C; c++)
-  {
-    // (bits + 7) / 8 would wrap for lengths near 2^64: compare without the rounding add
-    if (offsets[c + 1] < offsets[c] || bits[c] / 8 > offsets[c + 1] - offsets[c] || (bits[c] / 8 == offsets[c + 1] - offsets[c] && (bits[c] & 7) != 0))
-      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "offsets must grow and hold ceil(bits / 8) bytes per channel", hipSuccess);
-    if (offsets[c + 1] - offsets[c] > ((uint64_t)1 << 29) - 64)
-      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "a stream of more than 512 MiB", hipSuccess);
-  }
-  return DEGA_OK;
+  const char *const what = packed_input_fault(j.C, offsets, bits, ((uint64_t)1 << 29) - 64, "a stream of more than 512 MiB");
+  return what == nullptr ? DEGA_OK : fail(ctx, DEGA_ERROR_INVALID_VALUE, what, hipSuccess);
 }
 
 // ---- the group: one pipeline per device, a host thread each ------------------------------------------------------------------
@@ -1460,15 +1502,22 @@ static Shape shape_from_job(const dega_hip_job *job)
   return j;
 }
 
-// contiguous channel ranges [c_g, c_g+1), whole 512-channel workgroups where the batch allows
-static std::vector<size_t> split_channels(size_t C, size_t G)
+// how many of a group's members a call of C channels uses: those that get a workgroup's `granule` of channels
+static size_t members_for(const dega_hip_group *grp, size_t C, size_t granule)
+{
+  return std::max<size_t>(1, std::min<size_t>(grp->ctx.size(), (C + granule - 1) / granule));
+}
+
+// contiguous channel ranges [c_g, c_g+1) for G members, cut at whole workgroups of `granule` channels (the coder's 512:
+// only where that leaves every member two of them -- a smaller batch is shared evenly; LZMH's 256: always)
+static std::vector<size_t> split_channels(size_t C, size_t G, size_t granule = 512)
 {
   std::vector<size_t> cut(G + 1, 0);
   for (size_t g = 1; g < G; g++)
   {
     size_t c = C / G * g + std::min(C % G, g);
-    if (C >= G * 1024)
-      c = c / 512 * 512;
+    if (granule < 512 || C >= G * 2 * granule)
+      c = c / granule * granule;
     cut[g] = c;
   }
   cut[G] = C;
@@ -1526,17 +1575,37 @@ static dega_hip_group group_of_one(dega_hip_ctx *ctx)
 static EncodeSink packed_sink(uint8_t *packed, size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err)
 {
   EncodeSink sink;
-  sink.packed = packed;
-  sink.packed_cap = packed_cap;
-  sink.offsets = offsets;
-  sink.bits = out_bits;
-  sink.err = err;
+  static_cast<PackedOut &>(sink) = packed_out(packed, packed_cap, offsets, out_bits, err);
   if (offsets != nullptr)
     offsets[0] = 0;
   return sink;
 }
 
-static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samples, const EncodeSink &sink)
+// Host-side concatenate for a group whose members have each delivered their share into a buffer of their own: member g's
+// streams (member(g): offsets relative to its share, total, full, and its buffer as `packed`) go behind those of the members
+// in front of it.  Writes the call's offsets and total; its bytes unless it, or a member, is full.
+template <class Member>
+static void concat_members(const std::vector<size_t> &cut, Member member, PackedOut &out)
+{
+  const size_t G = cut.size() - 1;
+  out.total = 0;
+  out.full = false;
+  for (size_t g = 0; g < G; g++)
+  {
+    const PackedOut &m = member(g);
+    for (size_t i = 0; i < cut[g + 1] - cut[g]; i++)
+      out.offsets[cut[g] + i] = out.total + m.offsets[i];
+    out.total += m.total;
+    out.full = out.full || m.full;
+  }
+  out.offsets[cut[G]] = out.total;
+  out.full = out.full || out.total > out.packed_cap;
+  for (size_t g = 0; g < G && !out.full; g++)
+    if (member(g).total > 0)
+      memcpy(out.packed + out.offsets[cut[g]], member(g).packed, (size_t)member(g).total);
+}
+
+static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samples, EncodeSink sink)
 {
   if (grp == nullptr || grp->ctx.empty())
     return DEGA_ERROR_LIBRARY_INIT;
@@ -1548,13 +1617,14 @@ static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samp
     return DEGA_ERROR_INVALID_VALUE;
   const size_t esz = sample_bytes(j);
   // devices that get no channels are left out; a single device delivers as it goes (copies overlap the kernels)
-  const size_t G = std::max<size_t>(1, std::min<size_t>(grp->ctx.size(), (j.C + 511) / 512));
+  const size_t G = members_for(grp, j.C, 512);
   if (G == 1)
   {
     EncodeRun run;
     ret = encode_share(grp->ctx[0], j, samples, sink, true, run);
     return ret == DEGA_OK ? DEGA_OK : group_fail(grp, ret, grp->ctx[0], 0);
   }
+  // Several members: packed mode (slab mode is the single-context forms', which come as a group of one).
   // Rounds: what the devices can hold at once (samples + slabs resident until the sizes in front are known) -- by the
   // member with the least free memory, and with the bytes per channel that encode_share reserves
   size_t free_b = ~(size_t)0;
@@ -1570,13 +1640,12 @@ static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samp
   }
   const size_t per_channel = std::max(j.T * esz + 64, usual_cap(j)) + 16 + (j.cmajor ? std::max(usual_cap(j), j.T * esz) : usual_cap(j)) + 64 + 256;
   size_t round_channels = std::max<size_t>(G * 512, std::min<size_t>(j.C, free_b / 10 * 6 / per_channel * G / 512 * 512));
-  uint64_t base = 0;
-  bool out_full = false;
   for (size_t r0 = 0; r0 < j.C;)
   {
     const size_t rC = std::min(round_channels, j.C - r0);
     const std::vector<size_t> cut = split_channels(rC, G);
     std::vector<EncodeRun> runs(G);
+    std::vector<EncodeSink> ss(G); // the members' shares: sized, their streams resident (no buffer, so `full` says nothing)
     std::vector<int> rets(G, DEGA_OK);
     std::vector<std::vector<uint64_t>> rel(G);
     std::vector<std::thread> th;
@@ -1585,11 +1654,10 @@ static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samp
         Shape sj = j;
         sj.C = cut[g + 1] - cut[g];
         rel[g].assign(sj.C + 1, 0);
-        EncodeSink ss;
-        ss.offsets = rel[g].data();
-        ss.bits = sink.bits + r0 + cut[g];
-        ss.err = sink.err + r0 + cut[g];
-        rets[g] = encode_share(grp->ctx[g], sj, (const uint8_t *)samples + (r0 + cut[g]) * (j.cmajor ? j.ld : 1) * esz, ss, false, runs[g]);
+        ss[g].offsets = rel[g].data();
+        ss[g].bits = sink.bits + r0 + cut[g];
+        ss[g].err = sink.err + r0 + cut[g];
+        rets[g] = encode_share(grp->ctx[g], sj, (const uint8_t *)samples + (r0 + cut[g]) * (j.cmajor ? j.ld : 1) * esz, ss[g], false, runs[g]);
       });
     for (std::thread &t : th)
       t.join();
@@ -1611,41 +1679,19 @@ static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samp
     std::vector<uint64_t> dev_base(G);
     for (size_t g = 0; g < G; g++)
     {
-      dev_base[g] = base;
-      if (sink.offsets != nullptr)
-        for (size_t i = 0; i < cut[g + 1] - cut[g]; i++)
-          sink.offsets[r0 + cut[g] + i] = base + rel[g][i];
-      base += runs[g].total;
+      dev_base[g] = sink.total;
+      for (size_t i = 0; i < cut[g + 1] - cut[g]; i++)
+        sink.offsets[r0 + cut[g] + i] = sink.total + rel[g][i];
+      sink.total += ss[g].total;
     }
-    if (sink.slabs == nullptr && base > sink.packed_cap)
-      out_full = true;
-    if (out_full)
-    {
-      r0 += rC;
-      continue; // keep sizing
-    }
-    ret = on_members(grp, G, [&](size_t g) -> int {
-      if (sink.slabs == nullptr)
-        return encode_deliver(grp->ctx[g], runs[g], sink.packed, dev_base[g]);
-      std::vector<uint8_t> tmp((size_t)runs[g].total + 1);
-      const int r = encode_deliver(grp->ctx[g], runs[g], tmp.data(), 0);
-      for (size_t i = 0; r == DEGA_OK && i < cut[g + 1] - cut[g]; i++)
-      {
-        const size_t c = r0 + cut[g] + i, nb = (size_t)(rel[g][i + 1] - rel[g][i]);
-        if (nb > sink.slab_cap)
-          sink.err[c] = sink.err[c] == DEGA_OK ? DEGA_ERROR_MEMORY : sink.err[c];
-        if (nb > 0)
-          memcpy(sink.slabs + c * sink.slab_cap, tmp.data() + rel[g][i], std::min(nb, sink.slab_cap));
-      }
-      return r;
-    });
-    if (ret != DEGA_OK)
+    sink.full = sink.full || sink.total > sink.packed_cap;
+    if (!sink.full && // (else: keep sizing)
+        (ret = on_members(grp, G, [&](size_t g) -> int { return encode_deliver(grp->ctx[g], runs[g], sink.packed, dev_base[g]); })) != DEGA_OK)
       return ret;
     r0 += rC;
   }
-  if (sink.offsets != nullptr)
-    sink.offsets[j.C] = base;
-  if (out_full)
+  sink.offsets[j.C] = sink.total;
+  if (sink.full)
   {
     snprintf(grp->last_error, sizeof(grp->last_error), "packed buffer too small: offsets[C] holds the size needed");
     return DEGA_ERROR_MEMORY;
@@ -1663,7 +1709,7 @@ static int decode_on_group(dega_hip_group *grp, const Shape &j, const uint8_t *p
     return group_fail(grp, ret, grp->ctx[0], 0);
   if (err == nullptr || (samples == nullptr && j.C * j.T != 0))
     return DEGA_ERROR_INVALID_VALUE;
-  const size_t G = std::max<size_t>(1, std::min<size_t>(grp->ctx.size(), (j.C + 511) / 512));
+  const size_t G = members_for(grp, j.C, 512);
   const size_t osz = sample_bytes(j);
   const std::vector<size_t> cut = split_channels(j.C, G);
   return on_members(grp, G, [&](size_t g) -> int {
@@ -1759,27 +1805,21 @@ static int encode_levels_on_group(dega_hip_group *grp, const dega_hip_job *job, 
   }
   if (K == 0)
     return DEGA_OK;
-  const size_t G = std::max<size_t>(1, std::min<size_t>(grp->ctx.size(), (j.C + 511) / 512));
+  const size_t G = members_for(grp, j.C, 512);
+  PackedOut out[AGG_MAX_LEVELS]; // the call's outputs, level by level
+  for (size_t k = 0; k < K; k++)
+    out[k] = packed_out(packed[k], packed_cap[k], offsets[k], out_bits[k], err[k]);
   if (G == 1)
   {
-    LevelSink sink[AGG_MAX_LEVELS];
-    for (size_t k = 0; k < K; k++)
-    {
-      sink[k].packed = packed[k];
-      sink[k].packed_cap = packed_cap[k];
-      sink[k].offsets = offsets[k];
-      sink[k].bits = out_bits[k];
-      sink[k].err = err[k];
-    }
     bool sized;
-    ret = encode_levels_share(grp->ctx[0], j, num_values, K, samples, sink, sized);
+    ret = encode_levels_share(grp->ctx[0], j, num_values, K, samples, out, sized);
     return ret == DEGA_OK ? DEGA_OK : group_fail(grp, ret, grp->ctx[0], 0);
   }
   // Several members: contiguous channel ranges, one host thread each; every member delivers each level into a host
   // buffer of its own (no larger than the caller's: a share that does not fit there does not fit the call), and the
   // caller's packed[k] is filled by host-side copies once the sizes in front are known.
   const std::vector<size_t> cut = split_channels(j.C, G);
-  std::vector<std::vector<LevelSink>> sinks(G, std::vector<LevelSink>(K));
+  std::vector<std::vector<PackedOut>> sinks(G, std::vector<PackedOut>(K));
   std::vector<std::vector<std::unique_ptr<uint8_t[]>>> tmp(G);
   std::vector<std::vector<std::vector<uint64_t>>> rel(G, std::vector<std::vector<uint64_t>>(K));
   for (size_t g = 0; g < G; g++)
@@ -1793,12 +1833,7 @@ static int encode_levels_on_group(dega_hip_group *grp, const dega_hip_job *job, 
       const size_t room = std::min(packed_cap[k], n * usual_cap(lj));
       tmp[g][k].reset(new uint8_t[std::max<size_t>(room, 1)]);
       rel[g][k].assign(n + 1, 0);
-      LevelSink &s = sinks[g][k];
-      s.packed = tmp[g][k].get();
-      s.packed_cap = room;
-      s.offsets = rel[g][k].data();
-      s.bits = out_bits[k] + cut[g];
-      s.err = err[k] + cut[g];
+      sinks[g][k] = packed_out(tmp[g][k].get(), room, rel[g][k].data(), out_bits[k] + cut[g], err[k] + cut[g]);
     }
   }
   ret = on_members(grp, G, [&](size_t g) -> int {
@@ -1831,21 +1866,8 @@ static int encode_levels_on_group(dega_hip_group *grp, const dega_hip_job *job, 
   bool any_full = false;
   for (size_t k = 0; k < K; k++)
   {
-    uint64_t base = 0;
-    for (size_t g = 0; g < G; g++)
-    {
-      for (size_t i = 0; i < cut[g + 1] - cut[g]; i++)
-        offsets[k][cut[g] + i] = base + rel[g][k][i];
-      base += sinks[g][k].total;
-    }
-    offsets[k][j.C] = base;
-    bool full = base > packed_cap[k];
-    for (size_t g = 0; g < G; g++)
-      full = full || sinks[g][k].full;
-    any_full = any_full || full;
-    for (size_t g = 0; g < G && !full; g++)
-      if (sinks[g][k].total > 0)
-        memcpy(packed[k] + offsets[k][cut[g]], tmp[g][k].get(), (size_t)sinks[g][k].total);
+    concat_members(cut, [&](size_t g) -> const PackedOut & { return sinks[g][k]; }, out[k]);
+    any_full = any_full || out[k].full;
   }
   if (any_full)
   {
@@ -2212,8 +2234,7 @@ static ChunkPlan lzmh_plan(size_t C, size_t stride, size_t cap)
   return p;
 }
 
-static int lzmh_encode_share(dega_hip_ctx *ctx, const uint8_t *in, size_t stride, const uint64_t *in_len, size_t C, uint8_t *packed, size_t packed_cap,
-                             uint64_t *offsets, uint64_t *out_bits, int32_t *err, uint64_t *total_out)
+static int lzmh_encode_share(dega_hip_ctx *ctx, const uint8_t *in, size_t stride, const uint64_t *in_len, size_t C, PackedOut &out)
 {
   int ret;
   Pipeline *pl;
@@ -2222,10 +2243,10 @@ static int lzmh_encode_share(dega_hip_ctx *ctx, const uint8_t *in, size_t stride
     return ret;
   const size_t cap = dega_hip_lzmh_worst_case_bytes(stride);
   const ChunkPlan plan = lzmh_plan(C, stride, cap);
-  const bool in_pinned = is_pinned(in), out_pinned = is_pinned(packed);
+  const bool in_pinned = is_pinned(in), out_pinned = is_pinned(out.packed);
   std::vector<Chunk> chunks(plan.nchunks);
-  uint64_t running = 0;
-  bool out_full = false;
+  out.total = 0;
+  out.full = false;
   auto stage1 = [&](size_t k) -> int {
     Chunk &ch = chunks[k];
     ch.place(plan, C, k);
@@ -2243,42 +2264,24 @@ static int lzmh_encode_share(dega_hip_ctx *ctx, const uint8_t *in, size_t stride
     HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.a.p, in + ch.c0 * stride, ch.n * stride, ch.n * stride, 1, in_pinned), DEGA_ERROR_LIBRARY_CALL);
     if ((r = dega_hip_lzmh_encode_dev(ctx, (const uint8_t *)sl.a.p, stride, dm.counts, ch.n, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
       return r;
-    hipLaunchKernelGGL(dega_offsets_kernel, dim3(1), dim3(1024), 0, sl.s, dm.bits, ch.n, dm.offsets);
-    HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, hipMemcpyAsync(sl.hmeta.p, sl.meta.p, (2 * ch.n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, hipMemcpyAsync(hm.err, dm.err, ch.n * sizeof(int32_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
-    return DEGA_OK;
+    return sizes_home(ctx, sl.s, dm, ch.n, sl.hmeta.p); // (the lengths come back with the set, as they went up)
   };
   auto stage2 = [&](size_t k) -> int {
     const Chunk &ch = chunks[k];
     Slot &sl = pl->slot[ch.slot];
     MetaView hm(sl.hmeta.p, ch.n), dm(sl.meta.p, ch.n);
     HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-    const uint64_t tot = hm.offsets[ch.n];
-    for (size_t i = 0; i < ch.n; i++)
-    {
-      out_bits[ch.c0 + i] = hm.bits[i];
-      err[ch.c0 + i] = hm.err[i];
-      offsets[ch.c0 + i] = running + hm.offsets[i];
-    }
-    const uint64_t base = running;
-    running += tot;
-    if (running > packed_cap)
-      out_full = true; // keep sizing: the caller learns what it needs
-    if (out_full || tot == 0)
+    const size_t tot = (size_t)hm.offsets[ch.n];
+    uint64_t base;
+    if (!chunk_sized(out, ch.c0, ch.n, hm, base))
       return DEGA_OK;
-    HIP_TRY(ctx, sl.c.need((size_t)tot + 64), DEGA_ERROR_MEMORY);
-    GatherArgs g{(const uint8_t *)sl.b.p, cap, dm.offsets, ch.n, (uint8_t *)sl.c.p};
-    hipLaunchKernelGGL(dega_gather_kernel, dim3((unsigned)((ch.n + WAVES - 1) / WAVES)), dim3(BLOCK), 0, sl.s, g);
-    HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, rows_to_host(pl, sl.s, packed + base, (size_t)tot, sl.c.p, (size_t)tot, 1, out_pinned), DEGA_ERROR_LIBRARY_CALL);
-    return DEGA_OK;
+    HIP_TRY(ctx, sl.c.need(tot + 64), DEGA_ERROR_MEMORY);
+    return chunk_home(ctx, pl, sl.s, out.packed + base, out_pinned, tot, nullptr, sl.b.p, cap, dm.offsets, ch.n, sl.c.p);
   };
   if ((ret = run_chunks(plan.nchunks, (size_t)plan.nslots, stage1, stage2)) != DEGA_OK || (ret = finish_slots(ctx, pl, plan.nslots)) != DEGA_OK)
     return ret;
-  offsets[C] = running;
-  *total_out = running;
-  if (out_full)
+  out.offsets[C] = out.total;
+  if (out.full)
     return fail(ctx, DEGA_ERROR_MEMORY, "packed buffer too small: offsets[C] holds the size needed", hipSuccess);
   return DEGA_OK;
 }
@@ -2305,28 +2308,11 @@ static int lzmh_decode_share(dega_hip_ctx *ctx, const uint8_t *packed, const uin
     if ((r = slot_stream(ctx, sl)) != DEGA_OK)
       return r;
     HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL); // the pinned mirror is about to be rewritten
-    const uint64_t o0 = offsets[ch.c0], nbytes = offsets[ch.c0 + ch.n] - o0;
-    uint64_t longest = 0;
-    for (size_t i = 0; i < ch.n; i++)
-      longest = std::max<uint64_t>(longest, offsets[ch.c0 + i + 1] - offsets[ch.c0 + i]);
-    const size_t cap = ((size_t)longest + 16 + 3) & ~(size_t)3;
-    HIP_TRY(ctx, sl.a.need((size_t)nbytes + 64), DEGA_ERROR_MEMORY);
-    HIP_TRY(ctx, sl.b.need(ch.n * cap + 64), DEGA_ERROR_MEMORY);
+    size_t cap;
     HIP_TRY(ctx, sl.c.need(ch.n * stride + 64), DEGA_ERROR_MEMORY);
-    HIP_TRY(ctx, sl.meta.need(MetaView::bytes(ch.n)), DEGA_ERROR_MEMORY);
-    HIP_TRY(ctx, sl.hmeta.need(MetaView::bytes(ch.n)), DEGA_ERROR_MEMORY);
+    if ((r = chunk_in(ctx, pl, sl, sl.s, packed, offsets + ch.c0, in_bits + ch.c0, ch.n, in_pinned, 0, cap)) != DEGA_OK)
+      return r;
     MetaView hm(sl.hmeta.p, ch.n), dm(sl.meta.p, ch.n);
-    for (size_t i = 0; i < ch.n; i++)
-    {
-      hm.bits[i] = in_bits[ch.c0 + i];
-      hm.offsets[i] = offsets[ch.c0 + i] - o0;
-    }
-    hm.offsets[ch.n] = nbytes;
-    HIP_TRY(ctx, hipMemcpyAsync(sl.meta.p, sl.hmeta.p, (2 * ch.n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, sl.s), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.a.p, packed + o0, (size_t)nbytes, (size_t)nbytes, 1, in_pinned), DEGA_ERROR_LIBRARY_CALL);
-    GatherArgs g{(const uint8_t *)sl.b.p, cap, dm.offsets, ch.n, (uint8_t *)sl.a.p};
-    hipLaunchKernelGGL(dega_scatter_kernel, dim3((unsigned)((ch.n + WAVES - 1) / WAVES)), dim3(BLOCK), 0, sl.s, g);
-    HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
     if ((r = dega_hip_lzmh_decode_dev(ctx, (const uint8_t *)sl.b.p, cap, dm.bits, ch.n, (uint8_t *)sl.c.p, stride, dm.counts, dm.err, sl.s)) != DEGA_OK)
       return r;
     HIP_TRY(ctx, hipMemcpyAsync(hm.counts, dm.counts, ch.n * sizeof(uint64_t) + ch.n * sizeof(int32_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
@@ -2347,16 +2333,6 @@ static int lzmh_decode_share(dega_hip_ctx *ctx, const uint8_t *packed, const uin
     return DEGA_OK;
   };
   return run_chunks(plan.nchunks, (size_t)plan.nslots, stage1, stage2);
-}
-
-// contiguous channel ranges [c_g, c_g+1) for the G members of an LZMH call, cut at whole 256-channel workgroups
-static std::vector<size_t> lzmh_split_channels(size_t C, size_t G)
-{
-  std::vector<size_t> cut(G + 1, 0);
-  for (size_t g = 1; g < G; g++)
-    cut[g] = (C / G * g + std::min(C % G, g)) / 256 * 256;
-  cut[G] = C;
-  return cut;
 }
 
 static int lzmh_check(dega_hip_group *grp, size_t stride, bool encode)
@@ -2382,18 +2358,18 @@ extern "C" int dega_hip_group_lzmh_encode(dega_hip_group *grp, const uint8_t *in
   offsets[0] = 0;
   if (C == 0)
     return DEGA_OK;
-  const size_t G = std::max<size_t>(1, std::min<size_t>(grp->ctx.size(), (C + 255) / 256));
-  uint64_t total = 0;
+  const size_t G = members_for(grp, C, 256);
+  PackedOut out = packed_out(packed, packed_cap, offsets, out_bits, err);
   if (G == 1)
   {
-    ret = lzmh_encode_share(grp->ctx[0], in, stride, in_len, C, packed, packed_cap, offsets, out_bits, err, &total);
+    ret = lzmh_encode_share(grp->ctx[0], in, stride, in_len, C, out);
     return ret == DEGA_OK ? DEGA_OK : group_fail(grp, ret, grp->ctx[0], 0);
   }
   // every device codes its range of channels into a buffer of its own; the host puts them behind one another
-  const std::vector<size_t> cut = lzmh_split_channels(C, G);
+  const std::vector<size_t> cut = split_channels(C, G, 256);
   std::vector<std::vector<uint8_t>> tmp(G);
   std::vector<std::vector<uint64_t>> rel(G);
-  std::vector<uint64_t> tot(G, 0);
+  std::vector<PackedOut> share(G);
   ret = on_members(grp, G, [&](size_t g) -> int {
     const size_t n = cut[g + 1] - cut[g];
     uint64_t text = 0;
@@ -2401,23 +2377,13 @@ extern "C" int dega_hip_group_lzmh_encode(dega_hip_group *grp, const uint8_t *in
       text += in_len[cut[g] + i];
     tmp[g].resize((size_t)(text + text / 4 + 64 * n + 64)); // a stream is at most 10 bits per byte of text
     rel[g].assign(n + 1, 0);
-    return n == 0 ? DEGA_OK
-                  : lzmh_encode_share(grp->ctx[g], in + cut[g] * stride, stride, in_len + cut[g], n, tmp[g].data(), tmp[g].size(), rel[g].data(),
-                                      out_bits + cut[g], err + cut[g], &tot[g]);
+    share[g] = packed_out(tmp[g].data(), tmp[g].size(), rel[g].data(), out_bits + cut[g], err + cut[g]);
+    return n == 0 ? DEGA_OK : lzmh_encode_share(grp->ctx[g], in + cut[g] * stride, stride, in_len + cut[g], n, share[g]);
   });
   if (ret != DEGA_OK)
     return ret;
-  uint64_t base = 0;
-  for (size_t g = 0; g < G; g++)
-  {
-    for (size_t i = 0; i < cut[g + 1] - cut[g]; i++)
-      offsets[cut[g] + i] = base + rel[g][i];
-    if (base + tot[g] <= packed_cap && tot[g] > 0)
-      memcpy(packed + base, tmp[g].data(), (size_t)tot[g]);
-    base += tot[g];
-  }
-  offsets[C] = base;
-  if (base > packed_cap)
+  concat_members(cut, [&](size_t g) -> const PackedOut & { return share[g]; }, out);
+  if (out.full)
   {
     snprintf(grp->last_error, sizeof(grp->last_error), "packed buffer too small: offsets[C] holds the size needed");
     return DEGA_ERROR_MEMORY;
@@ -2435,15 +2401,13 @@ extern "C" int dega_hip_group_lzmh_decode(dega_hip_group *grp, const uint8_t *pa
     return DEGA_ERROR_INVALID_VALUE;
   if (C == 0)
     return DEGA_OK;
-  for (size_t c = 0; c < C; c++)
-    if (offsets[c + 1] < offsets[c] || in_bits[c] / 8 > offsets[c + 1] - offsets[c] || (in_bits[c] / 8 == offsets[c + 1] - offsets[c] && (in_bits[c] & 7) != 0) ||
-        offsets[c + 1] - offsets[c] > ((uint64_t)1 << 31))
-    {
-      snprintf(grp->last_error, sizeof(grp->last_error), "offsets must grow and hold ceil(bits / 8) bytes per channel");
-      return DEGA_ERROR_INVALID_VALUE;
-    }
-  const size_t G = std::max<size_t>(1, std::min<size_t>(grp->ctx.size(), (C + 255) / 256));
-  const std::vector<size_t> cut = lzmh_split_channels(C, G);
+  if (const char *const what = packed_input_fault(C, offsets, in_bits, (uint64_t)1 << 31, nullptr))
+  {
+    snprintf(grp->last_error, sizeof(grp->last_error), "%s", what);
+    return DEGA_ERROR_INVALID_VALUE;
+  }
+  const size_t G = members_for(grp, C, 256);
+  const std::vector<size_t> cut = split_channels(C, G, 256);
   return on_members(grp, G, [&](size_t g) -> int {
     const size_t n = cut[g + 1] - cut[g];
     return n == 0 ? DEGA_OK

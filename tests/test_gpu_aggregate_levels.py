@@ -301,7 +301,7 @@ def assert_same_job(got, want, tag):
 
 
 def test_encode_job_levels_equals_the_single_level_jobs(dca, ctx, monkeypatch):
-    """pageable and pinned samples, a context and groups of one and two members, a batch cut into several chunks"""
+    """pageable and pinned samples, a context and groups of one and two members, a wider batch under the chunk knob"""
     rng = np.random.default_rng(2719)
     T, Cn, levels = 240, 1100, [7, 1, 60, 2]  # 1 100 channels: a group of two members really splits them
     v = meter(rng, T, Cn, top=30.0)
@@ -322,7 +322,8 @@ def test_encode_job_levels_equals_the_single_level_jobs(dca, ctx, monkeypatch):
             got = who.encode_job_levels(widev, levels, adaptive=1, factor=100.0, channels=Cn)
             for k, N in enumerate(levels):
                 assert_same_job(got[k], want[k], (type(who).__name__, N, "channels"))
-        # several chunks on several slots (the knob the pipeline's own measurements use)
+        # the knob the pipeline's own measurements use, on a wider batch and a static model (2 600 channels are still one
+        # chunk -- none is narrower than min(C, 8192) channels; several chunks: test_gpu_pipeline_chunks.py)
         monkeypatch.setenv("DEGA_PIPELINE_CHUNKS", "3")
         wide = meter(rng, 96, 2600, top=30.0)
         got = ctx.encode_job_levels(wide, [2, 12, 5], adaptive=0, valuesize=16, factor=10.0)

@@ -179,12 +179,13 @@ def test_lzmh_long_channels_count_saturation_and_long_runs(ctx):
 
 
 def test_lzmh_group_pipeline_packs_and_splits(dca, ctx):
-    """dega_hip_group_lzmh_encode / _decode: the host pipeline (chunks of channels on their own streams, packed streams
-    back) on a group of one and of two members (with one visible GPU both share device 0: the partition, the threads and
-    the host-side concatenate are the same code): the packed streams are the single-context slab call's, byte for byte,
-    and decode to the text; pageable and pinned memory; a packed buffer too small reports the size needed."""
+    """dega_hip_group_lzmh_encode / _decode: the host pipeline (packed streams back) on a group of one and of two members
+    (with one visible GPU both share device 0: the partition, the threads and the host-side concatenate are the same
+    code): the packed streams are the single-context slab call's, byte for byte, and decode to the text; pageable and
+    pinned memory; a packed buffer too small reports the size needed.  Every member's share is ONE chunk here, whatever
+    DEGA_PIPELINE_CHUNKS says (no chunk is narrower than min(C, 8192) channels); several: test_gpu_pipeline_chunks.py."""
     rng = np.random.default_rng(321)
-    strings = make_strings(rng, 1100, 900)  # more than two 512-channel chunks
+    strings = make_strings(rng, 1100, 900)  # two members: 512 and 588 channels
     Cn = len(strings)
     stride = (max(len(s) for s in strings) + 16) // 16 * 16
     text = np.zeros((Cn, stride), dtype=np.uint8)

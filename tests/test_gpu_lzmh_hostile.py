@@ -108,8 +108,9 @@ def packed_form(streams, form):
 
 @pytest.mark.parametrize("devices", ([0], [0, 0]))
 def test_group_decode_of_the_packed_corpus_equals_the_slab_call(dca, ctx, devices):
-    """dega_hip_group_lzmh_decode: chunks of channels on their own streams, one member and two (both on device 0).  The
-    corpus (one chunk per member) and the copy grid (many)"""
+    """dega_hip_group_lzmh_decode: one member and two (both on device 0).  No chunk is narrower than min(C, 8192) channels
+    whatever DEGA_PIPELINE_CHUNKS says: the corpus (130 channels) is one chunk per member, and the copy grid (12 000 cells)
+    two chunks of 8 192 and 3 808 channels on one member, one chunk each on two.  More chunks: test_gpu_pipeline_chunks.py"""
     os.environ["DEGA_PIPELINE_CHUNKS"] = "3"
     g = dca.Group(devices)
     try:

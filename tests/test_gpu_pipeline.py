@@ -152,8 +152,10 @@ def test_pipeline_chunks_and_streams_equal_device_resident(dca, ctx):
 
 def test_order_of_the_enqueues_does_not_change_the_result(dca, ctx, monkeypatch):
     """How far the first stages of an encode call run ahead of the second ones (DEGA_PIPELINE_AHEAD), whether a decode
-    call's uploads go first on one stream (DEGA_PIPELINE_UPLOADS_FIRST) and how many chunks there are only change WHEN the
-    copies and kernels run: same packed streams, same samples back.  Pinned and pageable memory, a ragged last chunk."""
+    call's uploads go first on one stream (DEGA_PIPELINE_UPLOADS_FIRST) and the DEGA_PIPELINE_CHUNKS knob only change WHEN
+    the copies and kernels run: same packed streams, same samples back.  Pinned and pageable memory.  At 2 600 channels
+    every setting of the knob is ONE chunk (plan_chunks makes no chunk narrower than min(C, 8192) channels), so this is the
+    knobs' parsing and the one-chunk path; batches that really are cut are in test_gpu_pipeline_chunks.py."""
     import torch
     Cn, T = 2600, 4200
     x = ctx.synth(Cn, T, seed=5, S=80)
