@@ -20,6 +20,7 @@
 #pragma once
 
 #include "dega_intrinsics.hpp"
+#include "dega_launch.hpp"
 
 #include <stddef.h>
 
@@ -147,6 +148,75 @@ __global__ void __launch_bounds__(256) dega_aggregate_kernel(const AggregateArgs
   }
   if (k != 0) // the series ended inside a group: aggregate.c:21-22 writes what it has
     L::store(dst, sum, a.wide_out);
+}
+
+// ---- host side: how the aggregate kernels are launched (dega_launch.hpp) -----------------------------------------------------
+// One variant for this kernel, dega_aggregate_levels_kernel and dega_aggregate_var_kernel.
+struct AggregateVariant
+{
+  bool wide;       // the 16-byte form: four channels per lane
+  uint32_t levels; // levels summed in the pass (1 for this kernel)
+};
+
+// four channels per lane where every row allows aligned 16-byte loads that stay inside its C values; else one
+inline bool aggregate_wide(const float *v, size_t C, size_t ld)
+{
+  return C % 4 == 0 && ld % 4 == 0 && ((uintptr_t)v & 15u) == 0;
+}
+
+inline bool aggregate_wide_out(bool wide, const float *a, size_t ld_out)
+{
+  return wide && ld_out % 4 == 0 && ((uintptr_t)a & 15u) == 0;
+}
+
+inline size_t aggregate_gx(size_t C, bool wide)
+{
+  const size_t units = wide ? C / 4 : C;
+  return (units + AGG_BLOCK - 1) / AGG_BLOCK;
+}
+
+inline size_t aggregate_rows(size_t T, size_t N)
+{
+  return N == 0 ? 0 : T / N + (T % N != 0 ? 1 : 0);
+}
+
+// Ranges of output rows along y (the unit is an output row, so the ranges are cut at multiples of N): enough workgroups for
+// eight per CU where the batch has them, never more ranges than output rows.
+inline size_t aggregate_row_ranges(size_t C, size_t T_out, bool wide)
+{
+  const size_t gx = aggregate_gx(C, wide), want = (2048 + gx - 1) / gx;
+  const size_t most = T_out < 65535 ? T_out : 65535;
+  return most < want ? most : (want > 1 ? want : 1);
+}
+
+// `row_ranges`: aggregate_row_ranges, or what a test forces (at most T_out are used)
+inline AggregateArgs aggregate_args(const float *v, size_t C, size_t T, size_t ld, size_t N, float *a, size_t ld_out, bool wide, size_t row_ranges)
+{
+  AggregateArgs g;
+  g.v = v;
+  g.a = a;
+  g.C = C;
+  g.T = T;
+  g.ld = ld;
+  g.N = N;
+  g.T_out = aggregate_rows(T, N);
+  g.ld_out = ld_out;
+  if (row_ranges > g.T_out)
+    row_ranges = g.T_out;
+  g.rows_per_block = (g.T_out + row_ranges - 1) / row_ranges;
+  g.wide_out = aggregate_wide_out(wide, a, ld_out) ? 1u : 0u;
+  return g;
+}
+
+template <typename L>
+inline bool launch(const AggregateVariant &v, const AggregateArgs &a, L &&launch_one)
+{
+  const size_t gx = aggregate_gx(a.C, v.wide);
+  if (v.levels != 1 || gx > LAUNCH_MAX_GX)
+    return false;
+  const LaunchGrid grid{(uint32_t)gx, (uint32_t)((a.T_out + a.rows_per_block - 1) / a.rows_per_block)};
+  with_bools([&](auto wide) { launch_one(dega_aggregate_kernel<std::conditional_t<decltype(wide)::value, AggF4, float>>, grid, AGG_BLOCK, a); }, v.wide);
+  return true;
 }
 
 } // namespace dg

@@ -111,4 +111,74 @@ __global__ void __launch_bounds__(256) dega_aggregate_levels_kernel(const Aggreg
       L::store(dst[l], sum[l], a.wide_out[l]);
 }
 
+// ---- host side: how the kernel is launched (dega_launch.hpp) ----------------------------------------------------------------
+
+// f(std::integral_constant<uint32_t, n>()) for the n = 1 .. AGG_MAX_LEVELS levels of a pass
+template <typename F>
+inline void for_levels_of_pass(uint32_t n, F &&f)
+{
+  switch (n)
+  {
+    case 1: f(std::integral_constant<uint32_t, 1>()); break;
+    case 2: f(std::integral_constant<uint32_t, 2>()); break;
+    case 3: f(std::integral_constant<uint32_t, 3>()); break;
+    case 4: f(std::integral_constant<uint32_t, 4>()); break;
+    case 5: f(std::integral_constant<uint32_t, 5>()); break;
+    case 6: f(std::integral_constant<uint32_t, 6>()); break;
+    case 7: f(std::integral_constant<uint32_t, 7>()); break;
+    default: f(std::integral_constant<uint32_t, 8>()); break;
+  }
+}
+
+// One pass over the image: the levels it sums (as many as the variant says) and the base rows per range of the grid's y
+// dimension, a multiple of every N[l] or a value >= T.
+struct AggregatePass
+{
+  const float *v;
+  size_t C, T, ld, step;
+  const size_t *N;
+  float *const *a;
+  const size_t *ld_out;
+};
+
+// what AggregateLevelsArgs<n> and AggregateVarArgs<n> share: the image and the n levels of the pass
+template <typename Args>
+inline void fill_pass(Args &g, uint32_t n, bool wide, const AggregatePass &p)
+{
+  g.v = p.v;
+  g.C = p.C;
+  g.T = p.T;
+  g.ld = p.ld;
+  g.step = p.step;
+  const size_t top = p.T > 1 ? p.T : 1;
+  for (uint32_t l = 0; l < n; l++)
+  {
+    g.a[l] = p.a[l];
+    g.ld_out[l] = p.ld_out[l];
+    g.N[l] = (uint32_t)(p.N[l] < top ? p.N[l] : top);
+    g.wide_out[l] = aggregate_wide_out(wide, p.a[l], p.ld_out[l]) ? 1u : 0u;
+  }
+}
+
+// two to AGG_MAX_LEVELS levels (one level is dega_aggregate_kernel)
+template <typename L>
+inline bool launch(const AggregateVariant &v, const AggregatePass &p, L &&launch_one)
+{
+  const size_t gx = aggregate_gx(p.C, v.wide);
+  if (v.levels < 2 || v.levels > AGG_MAX_LEVELS || p.step == 0 || gx > LAUNCH_MAX_GX)
+    return false;
+  const LaunchGrid grid{(uint32_t)gx, (uint32_t)((p.T + p.step - 1) / p.step)};
+  for_levels_of_pass(v.levels, [&](auto levels) {
+    constexpr uint32_t NL = decltype(levels)::value;
+    if constexpr (NL >= 2)
+    {
+      AggregateLevelsArgs<NL> g;
+      fill_pass(g, NL, v.wide, p);
+      with_bools([&](auto wide) { launch_one(dega_aggregate_levels_kernel<std::conditional_t<decltype(wide)::value, AggF4, float>, NL>, grid, AGG_BLOCK, g); },
+                 v.wide);
+    }
+  });
+  return true;
+}
+
 } // namespace dg

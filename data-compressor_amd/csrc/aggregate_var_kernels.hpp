@@ -250,4 +250,40 @@ __global__ void __launch_bounds__(256) dega_aggregate_var_kernel(const Aggregate
       ends.store(dst[l], sum[l], first[l], a.wide_out[l]);
 }
 
+// ---- host side: how the kernel is launched (dega_launch.hpp) ----------------------------------------------------------------
+
+// what a counted pass has beside its AggregatePass
+struct AggregateCounts
+{
+  const uint64_t *count;
+  uint64_t *const *out_count; // one array per level of the pass
+  int32_t *err;               // the status is one pass's to write: null in every pass of a call but its first
+};
+
+// one to AGG_MAX_LEVELS levels; p.step 0 counts as 1, and an image without rows still has one range (the counts and the
+// status are the kernel's)
+template <typename L>
+inline bool launch(const AggregateVariant &v, const AggregatePass &pass, const AggregateCounts &c, L &&launch_one)
+{
+  const size_t gx = aggregate_gx(pass.C, v.wide);
+  if (v.levels < 1 || v.levels > AGG_MAX_LEVELS || gx > LAUNCH_MAX_GX)
+    return false;
+  AggregatePass p = pass;
+  p.step = p.step > 1 ? p.step : 1;
+  const size_t ranges = (p.T + p.step - 1) / p.step;
+  const LaunchGrid grid{(uint32_t)gx, (uint32_t)(ranges > 1 ? ranges : 1)};
+  for_levels_of_pass(v.levels, [&](auto levels) {
+    constexpr uint32_t NL = decltype(levels)::value;
+    AggregateVarArgs<NL> g;
+    fill_pass(g, NL, v.wide, p);
+    g.count = c.count;
+    g.err = c.err;
+    for (uint32_t l = 0; l < NL; l++)
+      g.out_count[l] = c.out_count[l];
+    with_bools([&](auto wide) { launch_one(dega_aggregate_var_kernel<std::conditional_t<decltype(wide)::value, AggF4, float>, NL>, grid, AGG_BLOCK, g); },
+               v.wide);
+  });
+  return true;
+}
+
 } // namespace dg

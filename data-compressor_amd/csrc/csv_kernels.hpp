@@ -31,6 +31,7 @@
 #pragma once
 
 #include "dega_intrinsics.hpp"
+#include "dega_launch.hpp"
 
 #include <stddef.h>
 
@@ -325,6 +326,52 @@ __global__ void __launch_bounds__(256) dega_csv_kernel(const CsvArgs a)
   }
   a.out_len[c] = VAR && over ? 0u : len;
   a.err[c] = VAR && over ? CSV_ERR_INVALID_VALUE : (ok ? CSV_OK : CSV_ERR_MEMORY);
+}
+
+// ---- host side: how the kernel is launched (dega_launch.hpp) ----------------------------------------------------------------
+struct CsvVariant
+{
+  bool wide_stores; // the LDS-staged 64-byte store form, else the 8-byte form (same bytes either way)
+  bool counted;     // a ragged batch: a count per channel
+};
+
+inline CsvVariant csv_variant(bool wide_stores, const uint64_t *count)
+{
+  return CsvVariant{wide_stores, count != nullptr};
+}
+
+inline CsvArgs csv_args(const float *v, size_t C, size_t T, size_t ld, unsigned decimals, size_t column, int separator_char, uint8_t *out, size_t stride,
+                        uint64_t *out_len, int32_t *err, const uint64_t *count)
+{
+  CsvArgs a;
+  a.v = v;
+  a.C = C;
+  a.T = T;
+  a.ld = ld;
+  a.decimals = decimals;
+  a.nsep = (uint32_t)(column - 1);
+  a.sep = (uint32_t)separator_char;
+  a.out = out;
+  a.stride = stride;
+  a.out_len = out_len;
+  a.err = err;
+  a.count = count;
+  return a;
+}
+
+template <typename L>
+inline bool launch(const CsvVariant &v, const CsvArgs &a, L &&launch_one)
+{
+  const size_t gx = (a.C + CSV_BLOCK - 1) / CSV_BLOCK;
+  if (gx > LAUNCH_MAX_GX || v.counted != (a.count != nullptr))
+    return false;
+  with_bools(
+      [&](auto wide, auto counted) {
+        launch_one(dega_csv_kernel<std::conditional_t<decltype(wide)::value, CsvStore64, CsvStore8>, decltype(counted)::value>, LaunchGrid{(uint32_t)gx, 1},
+                   CSV_BLOCK, a);
+      },
+      v.wide_stores, v.counted);
+  return true;
 }
 
 } // namespace dg

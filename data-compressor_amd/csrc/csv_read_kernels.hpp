@@ -41,6 +41,7 @@
 #pragma once
 
 #include "dega_intrinsics.hpp"
+#include "dega_launch.hpp"
 
 #include <stddef.h>
 
@@ -768,6 +769,35 @@ __global__ void __launch_bounds__(256) dega_csv_read_kernel(const CsvReadArgs a)
     return;
   a.out_count[c] = t;
   a.err[c] = status != CSVR_OK ? status : (t > a.max_T ? CSVR_ERR_MEMORY : CSVR_OK);
+}
+
+// ---- host side: how the kernel is launched (dega_launch.hpp); one instantiation ----------------------------------------------
+inline CsvReadArgs csv_read_args(const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column, int separator_char, float *v, size_t max_T,
+                                 size_t ld, uint64_t *out_count, int32_t *err)
+{
+  CsvReadArgs a;
+  a.text = text;
+  a.stride = stride;
+  a.len = len;
+  a.C = C;
+  a.column = column <= 0xFFFFFFFFu ? (uint32_t)column : 0u; // (no line has 2^32 fields: such a column selects nothing)
+  a.sep = (uint32_t)separator_char;
+  a.v = v;
+  a.max_T = max_T;
+  a.ld = ld;
+  a.out_count = out_count;
+  a.err = err;
+  return a;
+}
+
+template <typename L>
+inline bool launch(const CsvReadArgs &a, L &&launch_one)
+{
+  const size_t gx = (a.C + CSVR_BLOCK - 1) / CSVR_BLOCK;
+  if (gx > LAUNCH_MAX_GX)
+    return false;
+  launch_one(dega_csv_read_kernel, LaunchGrid{(uint32_t)gx, 1}, CSVR_BLOCK, a);
+  return true;
 }
 
 } // namespace dg

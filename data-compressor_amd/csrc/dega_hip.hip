@@ -81,18 +81,17 @@ static int fail(dega_hip_ctx *ctx, int code, const char *what, hipError_t e)
       return fail((ctx), (code), #expr, e_);          \
   } while (0)
 
-static void build_div_table(std::vector<uint32_t> &tab)
+// The library's backend of the launch descriptions at the foot of the kernel headers (dega_launch.hpp): the kernel on the
+// call's stream.  Every kernel of those headers is launched from here.
+struct OnStream
 {
-  tab.assign(DIV_TABLE_SIZE, 0u);
-  for (uint32_t t = 3; t < DIV_TABLE_SIZE; t++)
+  hipStream_t s;
+  template <typename A>
+  void operator()(void (*kernel)(A), LaunchGrid grid, uint32_t block, const A &a) const
   {
-    uint32_t L = 0;
-    while ((1u << L) < t)
-      L++;
-    const unsigned __int128 num = (unsigned __int128)1 << (30 + L);
-    tab[t] = (uint32_t)((num + t - 1) / t); // ceil(2^(30+L) / t); the shift L - 2 is recomputed from t (div_shift)
+    hipLaunchKernelGGL(kernel, dim3(grid.x, grid.y), dim3(block), 0, s, a);
   }
-}
+};
 
 extern "C" int dega_hip_device_count(void)
 {
@@ -315,19 +314,7 @@ static int check_job_shape(dega_hip_ctx *ctx, const Shape &j, size_t cap)
   return check_shape(ctx, j.C, j.T, j.cmajor ? j.C : j.ld, cap, 32);
 }
 
-template <bool AD, bool NARROW, bool F32>
-static void encode_launch(size_t C, hipStream_t s, const EncodeArgs &a)
-{
-  const dim3 grid((unsigned)((C + ENC_CHANNELS - 1) / ENC_CHANNELS));
-  // short channels (and enough of them to fill the chip twice): half the table, small rings, two workgroups per CU
-  if (AD && a.T <= ENC_SHORT_T && a.seg_state == nullptr && C > 65536)
-    hipLaunchKernelGGL((dega_encode_kernel<AD, NARROW, 4, 16, 8, 16, false, F32, ENC_PAIRS, ENC_SHORT_TABLE>), grid, dim3(ENC_BLOCK), 0, s, a);
-  else
-    hipLaunchKernelGGL((dega_encode_kernel<AD, NARROW, ENC_ROWS, ENC_RING, ENC_RAW, ENC_ORING, false, F32>), grid, dim3(ENC_BLOCK), 0, s, a);
-}
-
-// `batch_C`: the channel count the workgroup shape is chosen by (the whole batch's when this launch is one chunk of it)
-static int launch_encode(dega_hip_ctx *ctx, const void *x, const Shape &j, size_t batch_C, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err,
+static int launch_encode(dega_hip_ctx *ctx, const void *x, const Shape &j, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err,
                          hipStream_t s, uint32_t *seg_state = nullptr, uint32_t seg_flags = 0, const uint64_t *count = nullptr)
 {
   int ret;
@@ -338,87 +325,16 @@ static int launch_encode(dega_hip_ctx *ctx, const void *x, const Shape &j, size_
   if (j.C == 0)
     return DEGA_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  const int vs = j.valuesize;
-  EncodeArgs a;
-  a.x = reinterpret_cast<const int32_t *>(x);
-  a.C = j.C;
-  a.T = j.T;
-  a.ld = j.ld;
-  a.out = out;
-  a.cap = cap;
-  a.out_bits = out_bits;
-  a.err = err;
-  a.div_magic = ctx->div_magic;
-  a.valuesize = (uint32_t)vs;
-  a.big_endian = j.samples == DEGA_SAMPLES_BE32 ? 1u : 0u;
-  a.factor = j.factor;
-  a.seg_state = seg_state;
-  a.seg_flags = seg_flags;
-  a.count = count;
-  // the bounds of normalize.c:21, rounded to float by the host compiler exactly as the reference's are
-  a.lo = -(float)((uint64_t)1 << (vs - 1));
-  a.hi = (float)(((uint64_t)1 << (vs - 1)) - 1);
-  const bool f32 = j.samples == DEGA_SAMPLES_F32, ad = j.adaptive != 0;
-  (void)batch_C; // (one workgroup shape for every batch size)
+  const bool f32 = j.samples == DEGA_SAMPLES_F32;
+  const EncodeArgs a = encode_args(x, j.C, j.T, j.ld, out, cap, out_bits, err, ctx->div_magic, j.valuesize, j.samples == DEGA_SAMPLES_BE32, j.factor, seg_state,
+                                   seg_flags, count);
   {
     LaunchTimer lt(ctx, 0, s);
-    if (count != nullptr) // a ragged batch: the float entry at the standard shape, and its two 64-bit forms
-    {
-      const dim3 grid((unsigned)((j.C + ENC_CHANNELS - 1) / ENC_CHANNELS));
-      const int sel = vs > 32 ? (ad ? 5 : 4) : (ad ? 2 : 0) | (vs < 32 ? 1 : 0);
-      switch (sel)
-      {
-        case 0: hipLaunchKernelGGL((dega_encode_kernel<false, false, ENC_ROWS, ENC_RING, ENC_RAW, ENC_ORING, false, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
-        case 1: hipLaunchKernelGGL((dega_encode_kernel<false, true, ENC_ROWS, ENC_RING, ENC_RAW, ENC_ORING, false, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((dega_encode_kernel<true, false, ENC_ROWS, ENC_RING, ENC_RAW, ENC_ORING, false, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((dega_encode_kernel<true, true, ENC_ROWS, ENC_RING, ENC_RAW, ENC_ORING, false, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((dega_encode_kernel<false, false, 4, 32, 16, 32, true, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
-        default: hipLaunchKernelGGL((dega_encode_kernel<true, false, 4, 32, 16, 32, true, true, ENC_PAIRS, DIV_TABLE_SIZE, true>), grid, dim3(ENC_BLOCK), 0, s, a); break;
-      }
-    }
-    else if (vs > 32) // 64-bit values
-    {
-      const dim3 grid((unsigned)((j.C + ENC_CHANNELS - 1) / ENC_CHANNELS));
-      if (f32)
-      {
-        if (ad)
-          hipLaunchKernelGGL((dega_encode_kernel<true, false, 4, 32, 16, 32, true, true>), grid, dim3(ENC_BLOCK), 0, s, a);
-        else
-          hipLaunchKernelGGL((dega_encode_kernel<false, false, 4, 32, 16, 32, true, true>), grid, dim3(ENC_BLOCK), 0, s, a);
-      }
-      else if (ad)
-        hipLaunchKernelGGL((dega_encode_kernel<true, false, 4, 32, 16, 32, true, false>), grid, dim3(ENC_BLOCK), 0, s, a);
-      else
-        hipLaunchKernelGGL((dega_encode_kernel<false, false, 4, 32, 16, 32, true, false>), grid, dim3(ENC_BLOCK), 0, s, a);
-    }
-    else
-    {
-      const bool narrow = vs < 32; // the narrow variants mask the samples and range check against the value size
-      const int sel = (ad ? 4 : 0) | (narrow ? 2 : 0) | (f32 ? 1 : 0);
-      switch (sel)
-      {
-        case 0: encode_launch<false, false, false>(j.C, s, a); break;
-        case 1: encode_launch<false, false, true>(j.C, s, a); break;
-        case 2: encode_launch<false, true, false>(j.C, s, a); break;
-        case 3: encode_launch<false, true, true>(j.C, s, a); break;
-        case 4: encode_launch<true, false, false>(j.C, s, a); break;
-        case 5: encode_launch<true, false, true>(j.C, s, a); break;
-        case 6: encode_launch<true, true, false>(j.C, s, a); break;
-        default: encode_launch<true, true, true>(j.C, s, a); break;
-      }
-    }
+    if (!launch(encode_variant(j.C, j.T, seg_state != nullptr, count != nullptr, j.valuesize, f32, j.adaptive != 0), a, OnStream{s}))
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode: no kernel for this sample type and valuesize", hipSuccess);
   }
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
-}
-
-template <bool AD, bool NARROW, bool F32>
-static void decode_launch(bool wide, size_t C, hipStream_t s, const DecodeArgs &a)
-{
-  if (wide)
-    hipLaunchKernelGGL((dega_decode_kernel<AD, NARROW, false, F32, 8, false>), dim3((unsigned)((C + 511) / 512)), dim3(1024), 0, s, a);
-  else
-    hipLaunchKernelGGL((dega_decode_kernel<AD, NARROW, false, F32>), dim3((unsigned)((C + DEC_CHANNELS - 1) / DEC_CHANNELS)), dim3(DEC_BLOCK), 0, s, a);
 }
 
 static int launch_decode(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, const Shape &j, size_t batch_C, void *x,
@@ -430,58 +346,13 @@ static int launch_decode(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const
   if (j.C == 0)
     return DEGA_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  const int vs = j.valuesize;
-  DecodeArgs a;
-  a.in = in;
-  a.cap = cap;
-  a.in_bits = in_bits;
-  a.C = j.C;
-  a.T = j.T;
-  a.ld = j.ld;
-  a.x = reinterpret_cast<int32_t *>(x);
-  a.err = err;
-  a.div_magic = ctx->div_magic;
-  a.out_count = out_count;
-  a.valuesize = (uint32_t)vs;
-  a.big_endian = j.samples == DEGA_SAMPLES_BE32 ? 1u : 0u;
-  a.factor = j.factor;
-  a.rows_done = band_rows != 0 ? rows_done : nullptr;
-  a.band_rows = band_rows;
-  const bool f32 = j.samples == DEGA_SAMPLES_F32, ad = j.adaptive != 0;
-  const bool wide = ctx->force_waves == 8 || (ctx->force_waves == 0 && batch_C > 65536);
+  const bool f32 = j.samples == DEGA_SAMPLES_F32;
+  const DecodeArgs a = decode_args(in, cap, in_bits, j.C, j.T, j.ld, x, out_count, err, ctx->div_magic, j.valuesize, j.samples == DEGA_SAMPLES_BE32, j.factor,
+                                   rows_done, band_rows);
   {
     LaunchTimer lt(ctx, 1, s);
-    if (vs > 32)
-    {
-      const dim3 grid((unsigned)((j.C + DEC_CHANNELS - 1) / DEC_CHANNELS));
-      if (f32)
-      {
-        if (ad)
-          hipLaunchKernelGGL((dega_decode_kernel<true, false, true, true>), grid, dim3(DEC_BLOCK), 0, s, a);
-        else
-          hipLaunchKernelGGL((dega_decode_kernel<false, false, true, true>), grid, dim3(DEC_BLOCK), 0, s, a);
-      }
-      else if (ad)
-        hipLaunchKernelGGL((dega_decode_kernel<true, false, true, false>), grid, dim3(DEC_BLOCK), 0, s, a);
-      else
-        hipLaunchKernelGGL((dega_decode_kernel<false, false, true, false>), grid, dim3(DEC_BLOCK), 0, s, a);
-    }
-    else
-    {
-      const bool narrow = vs < 32;
-      const int sel = (ad ? 4 : 0) | (narrow ? 2 : 0) | (f32 ? 1 : 0);
-      switch (sel)
-      {
-        case 0: decode_launch<false, false, false>(wide, j.C, s, a); break;
-        case 1: decode_launch<false, false, true>(wide, j.C, s, a); break;
-        case 2: decode_launch<false, true, false>(wide, j.C, s, a); break;
-        case 3: decode_launch<false, true, true>(wide, j.C, s, a); break;
-        case 4: decode_launch<true, false, false>(wide, j.C, s, a); break;
-        case 5: decode_launch<true, false, true>(wide, j.C, s, a); break;
-        case 6: decode_launch<true, true, false>(wide, j.C, s, a); break;
-        default: decode_launch<true, true, true>(wide, j.C, s, a); break;
-      }
-    }
+    if (!launch(decode_variant(batch_C, ctx->force_waves, j.valuesize, f32, j.adaptive != 0), a, OnStream{s}))
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "decode: no kernel for this sample type and valuesize", hipSuccess);
   }
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
@@ -508,7 +379,7 @@ extern "C" int dega_hip_encode_dev(dega_hip_ctx *ctx, const int32_t *x_tc, size_
   int ret;
   if ((ret = check_shape(ctx, C, T, ld, cap, valuesize)) != DEGA_OK)
     return ret;
-  return launch_encode(ctx, x_tc, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_I32), C, out, cap, out_bits, err, (hipStream_t)stream);
+  return launch_encode(ctx, x_tc, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_I32), out, cap, out_bits, err, (hipStream_t)stream);
 }
 
 extern "C" size_t dega_hip_encode_state_bytes(size_t C)
@@ -525,7 +396,7 @@ extern "C" int dega_hip_encode_segment_dev(dega_hip_ctx *ctx, const int32_t *x_t
   if (state == nullptr || (flags & ~(unsigned)(DEGA_SEGMENT_CONTINUES | DEGA_SEGMENT_MORE)) != 0u || ((uintptr_t)state & 3u) != 0)
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode segment: state (device memory, dega_hip_encode_state_bytes) and flags DEGA_SEGMENT_*", hipSuccess);
   static_assert(DEGA_SEGMENT_CONTINUES == ENC_SEG_CONTINUES && DEGA_SEGMENT_MORE == ENC_SEG_MORE, "the flags of the header are the kernel's");
-  return launch_encode(ctx, x_tc, shape_of(C, T_seg, ld, adaptive, valuesize, DEGA_SAMPLES_I32), C, out, cap, out_bits, err, (hipStream_t)stream,
+  return launch_encode(ctx, x_tc, shape_of(C, T_seg, ld, adaptive, valuesize, DEGA_SAMPLES_I32), out, cap, out_bits, err, (hipStream_t)stream,
                        (uint32_t *)state, flags);
 }
 
@@ -552,7 +423,7 @@ extern "C" int dega_hip_decode_var_dev(dega_hip_ctx *ctx, const uint8_t *in, siz
 extern "C" int dega_hip_encode_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, float factor, int adaptive, int valuesize,
                                        uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream)
 {
-  return launch_encode(ctx, v_tc, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor), C, out, cap, out_bits, err, (hipStream_t)stream);
+  return launch_encode(ctx, v_tc, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor), out, cap, out_bits, err, (hipStream_t)stream);
 }
 
 extern "C" int dega_hip_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld,
@@ -568,18 +439,8 @@ extern "C" int dega_hip_encode_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc,
     return DEGA_ERROR_INVALID_VALUE;
   if (count == nullptr && C != 0)
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode: count must be a device array of C entries", hipSuccess);
-  return launch_encode(ctx, v_tc, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor), C, out, cap, out_bits, err, (hipStream_t)stream, nullptr, 0,
+  return launch_encode(ctx, v_tc, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_F32, factor), out, cap, out_bits, err, (hipStream_t)stream, nullptr, 0,
                        count);
-}
-
-static dim3 rowsplit_grid(size_t C, size_t T)
-{
-  // enough blocks to fill the chip: columns x row-chunks
-  const unsigned gx = (unsigned)((C + BLOCK - 1) / BLOCK);
-  unsigned gy = 1;
-  while ((size_t)gx * gy < 2048 && gy < 1024 && (size_t)gy * 64 < T)
-    gy *= 2;
-  return dim3(gx, gy);
 }
 
 extern "C" int dega_hip_normalize_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, float factor, int valuesize,
@@ -595,10 +456,7 @@ extern "C" int dega_hip_normalize_dev(dega_hip_ctx *ctx, const float *v_tc, size
   HIP_TRY(ctx, hipMemsetAsync(err, 0, C * sizeof(int32_t), s), DEGA_ERROR_LIBRARY_CALL);
   if (T == 0)
     return DEGA_OK;
-  // the bounds of normalize.c:21, rounded to float by the host compiler exactly as the reference's are
-  const float lo = -(float)((uint64_t)1 << (valuesize - 1)), hi = (float)(((uint64_t)1 << (valuesize - 1)) - 1);
-  NormalizeArgs a{v_tc, x_tc, C, T, ld, factor, err, lo, hi, valuesize >= 32 ? 0xFFFFFFFFu : (1u << valuesize) - 1u};
-  hipLaunchKernelGGL(dega_normalize_kernel, rowsplit_grid(C, T), dim3(BLOCK), 0, s, a);
+  launch(normalize_args(v_tc, x_tc, C, T, ld, factor, err, valuesize), rowsplit_ranges(C, T), OnStream{s});
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
 }
@@ -612,8 +470,7 @@ extern "C" int dega_hip_denormalize_dev(dega_hip_ctx *ctx, const int32_t *x_tc, 
   if (C == 0 || T == 0)
     return DEGA_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  DenormalizeArgs a{x_tc, v_tc, C, T, ld, factor, (uint32_t)(32 - valuesize)};
-  hipLaunchKernelGGL(dega_denormalize_kernel, rowsplit_grid(C, T), dim3(BLOCK), 0, (hipStream_t)stream, a);
+  launch(denormalize_args(x_tc, v_tc, C, T, ld, factor, valuesize), rowsplit_ranges(C, T), OnStream{(hipStream_t)stream});
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
 }
@@ -636,8 +493,6 @@ static size_t image_bytes(size_t rows, size_t ld, size_t C)
   return ((rows - 1) * ld + C) * sizeof(float);
 }
 
-// Columns x ranges of output rows (the pattern of rowsplit_grid, cut at multiples of num_values because the unit is an
-// output row): enough workgroups for eight per CU where the batch has them, never more ranges than output rows.
 static int launch_aggregate(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t N, float *a_tc, size_t ld_out, hipStream_t s)
 {
   if (ctx == nullptr)
@@ -659,30 +514,9 @@ static int launch_aggregate(dega_hip_ctx *ctx, const float *v_tc, size_t C, size
       return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: a_tc overlaps v_tc", hipSuccess);
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  // four channels per lane where every row allows aligned 16-byte loads that stay inside its C values; else one
-  const bool wide = C % 4 == 0 && ld % 4 == 0 && ((uintptr_t)v_tc & 15u) == 0;
-  const size_t units = wide ? C / 4 : C;
-  const size_t gx = (units + AGG_BLOCK - 1) / AGG_BLOCK;
-  if (gx > 0x7FFFFFFFu)
+  const bool wide = aggregate_wide(v_tc, C, ld);
+  if (!launch(AggregateVariant{wide, 1}, aggregate_args(v_tc, C, T, ld, N, a_tc, ld_out, wide, aggregate_row_ranges(C, T_out, wide)), OnStream{s}))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate: too many channels for one launch", hipSuccess);
-  size_t gy = std::min<size_t>(std::min<size_t>(T_out, 65535), std::max<size_t>(1, (2048 + gx - 1) / gx));
-  AggregateArgs a;
-  a.v = v_tc;
-  a.a = a_tc;
-  a.C = C;
-  a.T = T;
-  a.ld = ld;
-  a.N = N;
-  a.T_out = T_out;
-  a.ld_out = ld_out;
-  a.rows_per_block = (T_out + gy - 1) / gy;
-  gy = (T_out + a.rows_per_block - 1) / a.rows_per_block;
-  a.wide_out = (wide && ld_out % 4 == 0 && ((uintptr_t)a_tc & 15u) == 0) ? 1u : 0u;
-  const dim3 grid((unsigned)gx, (unsigned)gy);
-  if (wide)
-    hipLaunchKernelGGL(dega_aggregate_kernel<AggF4>, grid, dim3(AGG_BLOCK), 0, s, a);
-  else
-    hipLaunchKernelGGL(dega_aggregate_kernel<float>, grid, dim3(AGG_BLOCK), 0, s, a);
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
 }
@@ -694,20 +528,6 @@ extern "C" int dega_hip_aggregate_dev(dega_hip_ctx *ctx, const float *v_tc, size
 }
 
 // ---- channel-major <-> time-major ---------------------------------------------------------------------------------------
-
-template <typename E>
-static void transpose_launch(bool wide_ld, bool wide_st, dim3 grid, hipStream_t s, const TransposeArgs &a)
-{
-  constexpr uint32_t V = 16 / sizeof(E);
-  if (wide_ld && wide_st)
-    hipLaunchKernelGGL((dega_transpose_kernel<E, V, V>), grid, dim3(TR_BLOCK), 0, s, a);
-  else if (wide_ld)
-    hipLaunchKernelGGL((dega_transpose_kernel<E, V, 1>), grid, dim3(TR_BLOCK), 0, s, a);
-  else if (wide_st)
-    hipLaunchKernelGGL((dega_transpose_kernel<E, 1, V>), grid, dim3(TR_BLOCK), 0, s, a);
-  else
-    hipLaunchKernelGGL((dega_transpose_kernel<E, 1, 1>), grid, dim3(TR_BLOCK), 0, s, a);
-}
 
 // S[R][sp] -> D[K][dp], D[k][r] = S[r][k]; the channel (what `count` is indexed by) is the source row when channel_rows.
 // to time-major: R = C, K = T; to channel-major: R = T, K = C.
@@ -737,26 +557,8 @@ static int launch_transpose(dega_hip_ctx *ctx, const void *src, size_t R, size_t
       return fail(ctx, DEGA_ERROR_INVALID_VALUE, "transpose: source and destination overlap", hipSuccess);
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  TransposeArgs a;
-  a.src = src;
-  a.dst = dst;
-  a.R = R;
-  a.K = K;
-  a.sp = sp;
-  a.dp = dp;
-  a.count = count;
-  a.count_on_rows = channel_rows ? 1u : 0u;
-  uint32_t gx, gy;
-  if (!tr_plan(R, K, TR_GRID_X, a, gx, gy))
+  if (!launch(transpose_variant(src, sp, dst, dp, esz), transpose_args(src, R, K, sp, count, channel_rows, dst, dp), TR_GRID_X, OnStream{s}))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "transpose: too many tiles for one launch", hipSuccess);
-  // 16-byte loads / stores on each side whose every row starts on a 16-byte boundary (a vector that crosses the edge of
-  // the logical region is done by elements in its lane, so the extents do not matter)
-  const size_t V = 16 / esz;
-  const bool wide_ld = ((uintptr_t)src & 15u) == 0 && sp % V == 0, wide_st = ((uintptr_t)dst & 15u) == 0 && dp % V == 0;
-  if (esz == 4)
-    transpose_launch<uint32_t>(wide_ld, wide_st, dim3(gx, gy), s, a);
-  else
-    transpose_launch<uint64_t>(wide_ld, wide_st, dim3(gx, gy), s, a);
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
 }
@@ -834,12 +636,6 @@ static size_t levels_min_workgroups() // DEGA_AGG_LEVELS_MIN_WORKGROUPS=n: measu
   return v >= 1 ? (size_t)v : AGG_LEVELS_MIN_WORKGROUPS;
 }
 
-static size_t agg_gx(size_t C, bool wide)
-{
-  const size_t units = wide ? C / 4 : C;
-  return (units + AGG_BLOCK - 1) / AGG_BLOCK;
-}
-
 static size_t gcd_of(size_t x, size_t y)
 {
   while (y != 0)
@@ -889,7 +685,7 @@ static int check_level_list(const size_t *num_values, size_t K)
 // pass: measured, eight levels in one pass take 14.1 ms where two passes of four take 16.4.
 static void plan_levels(size_t C, size_t T, const size_t *num_values, size_t K, bool wide, LevelsPlan &p)
 {
-  const size_t gx = std::max<size_t>(agg_gx(C, wide), 1), Tn = std::max<size_t>(T, 1);
+  const size_t gx = std::max<size_t>(aggregate_gx(C, wide), 1), Tn = std::max<size_t>(T, 1);
   const size_t min_workgroups = levels_min_workgroups();
   size_t order[AGG_MAX_LEVELS], L_of[AGG_MAX_LEVELS], members[AGG_MAX_LEVELS];
   for (size_t k = 0; k < K; k++)
@@ -967,7 +763,7 @@ static int check_levels_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size
     return DEGA_OK;
   if (!f32_array(v_tc))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: v_tc must be a float32 device array", hipSuccess);
-  if (agg_gx(C, false) > 0x7FFFFFFFu)
+  if (aggregate_gx(C, false) > 0x7FFFFFFFu)
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: too many channels for one launch", hipSuccess);
   uintptr_t lo[AGG_MAX_LEVELS + 1], hi[AGG_MAX_LEVELS + 1];
   lo[K] = (uintptr_t)v_tc;
@@ -1006,42 +802,6 @@ static int check_counts(dega_hip_ctx *ctx, size_t C, size_t T, const uint64_t *c
   return DEGA_OK;
 }
 
-// f(std::integral_constant<uint32_t, n>()) for the n = 1 .. AGG_MAX_LEVELS levels of a pass
-template <typename F>
-static void for_levels_of_pass(uint32_t n, F &&f)
-{
-  switch (n)
-  {
-    case 1: f(std::integral_constant<uint32_t, 1>()); break;
-    case 2: f(std::integral_constant<uint32_t, 2>()); break;
-    case 3: f(std::integral_constant<uint32_t, 3>()); break;
-    case 4: f(std::integral_constant<uint32_t, 4>()); break;
-    case 5: f(std::integral_constant<uint32_t, 5>()); break;
-    case 6: f(std::integral_constant<uint32_t, 6>()); break;
-    case 7: f(std::integral_constant<uint32_t, 7>()); break;
-    default: f(std::integral_constant<uint32_t, 8>()); break;
-  }
-}
-
-// what AggregateLevelsArgs<n> and AggregateVarArgs<n> share: the image and the n levels of the pass
-template <typename Args>
-static void fill_pass(Args &a, uint32_t n, const float *v_tc, size_t C, size_t T, size_t ld, size_t step, bool wide, const size_t *N, float *const *a_tc,
-                      const size_t *ld_out)
-{
-  a.v = v_tc;
-  a.C = C;
-  a.T = T;
-  a.ld = ld;
-  a.step = step;
-  for (uint32_t l = 0; l < n; l++)
-  {
-    a.a[l] = a_tc[l];
-    a.ld_out[l] = ld_out[l];
-    a.N[l] = (uint32_t)std::min(N[l], std::max<size_t>(T, 1));
-    a.wide_out[l] = (wide && ld_out[l] % 4 == 0 && ((uintptr_t)a_tc[l] & 15u) == 0) ? 1u : 0u;
-  }
-}
-
 // The passes of the plan on s.  `count`, `out_count` and `err` are null for a uniform batch; with them the passes (planned
 // on T, as for the uniform call) go through the counted kernel.  The arguments have been through check_levels_dev and,
 // for a counted batch, check_counts.
@@ -1051,7 +811,7 @@ static int launch_aggregate_levels(dega_hip_ctx *ctx, const float *v_tc, size_t 
   if (K == 0 || C == 0 || (T == 0 && count == nullptr)) // (a counted batch still launches at T = 0: the counts and the status are the kernel's)
     return DEGA_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  const bool wide = C % 4 == 0 && ld % 4 == 0 && ((uintptr_t)v_tc & 15u) == 0; // as launch_aggregate
+  const bool wide = aggregate_wide(v_tc, C, ld);
   LevelsPlan p;
   plan_levels(C, T, num_values, K, wide, p);
   for (int q = 0; q < p.passes; q++)
@@ -1076,35 +836,11 @@ static int launch_aggregate_levels(dega_hip_ctx *ctx, const float *v_tc, size_t 
         return ret;
       continue;
     }
-    for_levels_of_pass(n, [&](auto levels) {
-      constexpr uint32_t NL = decltype(levels)::value;
-      if (count != nullptr)
-      {
-        AggregateVarArgs<NL> g;
-        const size_t step = std::max<size_t>(p.step_of[q], 1);
-        fill_pass(g, NL, v_tc, C, T, ld, step, wide, N, a, ldo);
-        g.count = count;
-        g.err = q == 0 ? err : nullptr; // the status is one pass's to write
-        for (uint32_t l = 0; l < NL; l++)
-          g.out_count[l] = oc[l];
-        const dim3 grid((unsigned)agg_gx(C, wide), (unsigned)std::max<size_t>(1, (T + step - 1) / step));
-        if (wide)
-          hipLaunchKernelGGL((dega_aggregate_var_kernel<AggF4, NL>), grid, dim3(AGG_BLOCK), 0, s, g);
-        else
-          hipLaunchKernelGGL((dega_aggregate_var_kernel<float, NL>), grid, dim3(AGG_BLOCK), 0, s, g);
-      }
-      else if constexpr (NL >= 2)
-      {
-        AggregateLevelsArgs<NL> g;
-        const size_t step = p.step_of[q];
-        fill_pass(g, NL, v_tc, C, T, ld, step, wide, N, a, ldo);
-        const dim3 grid((unsigned)agg_gx(C, wide), (unsigned)((T + step - 1) / step));
-        if (wide)
-          hipLaunchKernelGGL((dega_aggregate_levels_kernel<AggF4, NL>), grid, dim3(AGG_BLOCK), 0, s, g);
-        else
-          hipLaunchKernelGGL((dega_aggregate_levels_kernel<float, NL>), grid, dim3(AGG_BLOCK), 0, s, g);
-      }
-    });
+    const AggregatePass pass{v_tc, C, T, ld, p.step_of[q], N, a, ldo};
+    // (counted: the status is one pass's to write)
+    if (!(count != nullptr ? launch(AggregateVariant{wide, n}, pass, AggregateCounts{count, oc, q == 0 ? err : nullptr}, OnStream{s})
+                           : launch(AggregateVariant{wide, n}, pass, OnStream{s})))
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "aggregate levels: too many channels for one launch", hipSuccess);
     HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   }
   return DEGA_OK;
@@ -1261,11 +997,11 @@ static int encode_levels(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t 
       {
         if (count != nullptr) // coded from v_tc with `count` itself
           hipLaunchKernelGGL(dega_level_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, count, C, T, out_count[k]);
-        ret = launch_encode(ctx, v_tc, j[k], C, out[k], cap[k], out_bits[k], err[k], s, nullptr, 0, count);
+        ret = launch_encode(ctx, v_tc, j[k], out[k], cap[k], out_bits[k], err[k], s, nullptr, 0, count);
         continue;
       }
       // (counted: a channel whose count is above T has level counts of 0: it is coded as empty, and the status launch names it)
-      ret = launch_encode(ctx, sums.a[i++], j[k], C, out[k], cap[k], out_bits[k], err[k], s, nullptr, 0, count != nullptr ? out_count[k] : nullptr);
+      ret = launch_encode(ctx, sums.a[i++], j[k], out[k], cap[k], out_bits[k], err[k], s, nullptr, 0, count != nullptr ? out_count[k] : nullptr);
       if (count != nullptr && ret == DEGA_OK)
         ret = launch_status(ctx, first, C, err[k], out_bits[k], s);
     }
@@ -1353,7 +1089,7 @@ extern "C" int dega_hip_synth_dev(dega_hip_ctx *ctx, int32_t *x_tc, size_t C, si
     return DEGA_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
   SynthArgs a{x_tc, C, T, ld, seed, c0, S};
-  hipLaunchKernelGGL(dega_synth_kernel, dim3((unsigned)((C + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, a);
+  launch(a, OnStream{(hipStream_t)stream});
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
 }
@@ -1375,7 +1111,7 @@ extern "C" int dega_hip_encode64_dev(dega_hip_ctx *ctx, const int64_t *x_tc, siz
   int ret;
   if ((ret = check_shape64(ctx, C, T, ld, cap, valuesize)) != DEGA_OK)
     return ret;
-  return launch_encode(ctx, x_tc, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_I64), C, out, cap, out_bits, err, (hipStream_t)stream);
+  return launch_encode(ctx, x_tc, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_I64), out, cap, out_bits, err, (hipStream_t)stream);
 }
 
 extern "C" int dega_hip_decode64_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld,
@@ -1424,7 +1160,7 @@ extern "C" int dega_hip_lzmh_encode_dev(dega_hip_ctx *ctx, const uint8_t *in, si
   hipStream_t s = (hipStream_t)stream;
   {
     LaunchTimer lt(ctx, 2, s);
-    hipLaunchKernelGGL(lzmh_encode_kernel, dim3((unsigned)((C + LZ_BLOCK - 1) / LZ_BLOCK)), dim3(LZ_ENC_THREADS), 0, s, a);
+    launch(a, OnStream{s});
   }
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
@@ -1444,7 +1180,7 @@ extern "C" int dega_hip_lzmh_decode_dev(dega_hip_ctx *ctx, const uint8_t *in, si
   hipStream_t s = (hipStream_t)stream;
   {
     LaunchTimer lt(ctx, 3, s);
-    hipLaunchKernelGGL(lzmh_decode_kernel, dim3((unsigned)((C + LZ_BLOCK - 1) / LZ_BLOCK)), dim3(LZD_THREADS), 0, s, a);
+    launch(a, OnStream{s});
   }
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
@@ -1459,7 +1195,7 @@ extern "C" int dega_hip_lzmh_render_dev(dega_hip_ctx *ctx, const int32_t *x_tc, 
     return DEGA_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
   RenderArgs a{x_tc, C, T, ld, out, stride, out_len, err};
-  hipLaunchKernelGGL(lzmh_render_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  launch(a, OnStream{(hipStream_t)stream});
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
 }
@@ -1515,33 +1251,8 @@ static int check_csv_options(dega_hip_ctx *ctx, size_t C, size_t ld, unsigned de
 static int launch_csv(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column, int separator_char,
                       uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, hipStream_t s, const uint64_t *count = nullptr)
 {
-  const size_t gx = (C + CSV_BLOCK - 1) / CSV_BLOCK;
-  if (gx > 0x7FFFFFFFu)
+  if (!launch(csv_variant(csv_wide_stores(), count), csv_args(v_tc, C, T, ld, decimals, column, separator_char, out, stride, out_len, err, count), OnStream{s}))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: too many channels for one launch", hipSuccess);
-  CsvArgs a;
-  a.v = v_tc;
-  a.C = C;
-  a.T = T;
-  a.ld = ld;
-  a.decimals = decimals;
-  a.nsep = (uint32_t)(column - 1);
-  a.sep = (uint32_t)separator_char;
-  a.out = out;
-  a.stride = stride;
-  a.out_len = out_len;
-  a.err = err;
-  a.count = count;
-  if (count != nullptr) // a ragged batch
-  {
-    if (csv_wide_stores())
-      hipLaunchKernelGGL((dega_csv_kernel<CsvStore64, true>), dim3((unsigned)gx), dim3(CSV_BLOCK), 0, s, a);
-    else
-      hipLaunchKernelGGL((dega_csv_kernel<CsvStore8, true>), dim3((unsigned)gx), dim3(CSV_BLOCK), 0, s, a);
-  }
-  else if (csv_wide_stores())
-    hipLaunchKernelGGL(dega_csv_kernel<CsvStore64>, dim3((unsigned)gx), dim3(CSV_BLOCK), 0, s, a);
-  else
-    hipLaunchKernelGGL(dega_csv_kernel<CsvStore8>, dim3((unsigned)gx), dim3(CSV_BLOCK), 0, s, a);
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
 }
@@ -1812,22 +1523,8 @@ static int check_csv_read_options(dega_hip_ctx *ctx, size_t C, size_t column, in
 static int launch_csv_read(dega_hip_ctx *ctx, const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column, int separator_char,
                            float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, int32_t *err, hipStream_t s)
 {
-  const size_t gx = (C + CSVR_BLOCK - 1) / CSVR_BLOCK;
-  if (gx > 0x7FFFFFFFu)
+  if (!launch(csv_read_args(text, stride, len, C, column, separator_char, v_tc, max_T, ld, out_count, err), OnStream{s}))
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: too many channels for one launch", hipSuccess);
-  CsvReadArgs a;
-  a.text = text;
-  a.stride = stride;
-  a.len = len;
-  a.C = C;
-  a.column = column <= 0xFFFFFFFFu ? (uint32_t)column : 0u; // (no line has 2^32 fields: such a column selects nothing)
-  a.sep = (uint32_t)separator_char;
-  a.v = v_tc;
-  a.max_T = max_T;
-  a.ld = ld;
-  a.out_count = out_count;
-  a.err = err;
-  hipLaunchKernelGGL(dega_csv_read_kernel, dim3((unsigned)gx), dim3(CSVR_BLOCK), 0, s, a);
   HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
   return DEGA_OK;
 }

@@ -19,10 +19,12 @@
 #pragma once
 
 #include "dega_lane.hpp"
+#include "dega_launch.hpp"
 
 #include <stddef.h>
 
 #include <type_traits>
+#include <vector>
 
 namespace dg
 {
@@ -426,7 +428,7 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
         wait_vector_memory();
         fill_batch();
 #if defined(DEGA_SIM)
-        if constexpr (VAR)
+        if constexpr (VAR || (W64 && F32IN)) // (the other variants vote inside fill_batch, after their reads)
           (void)wave_any(false); // (the emulator's lanes are threads: all of them have read their rows before one fetches into the others' columns)
 #endif
         if (t < T_end)
@@ -1847,6 +1849,215 @@ __global__ void __launch_bounds__(256) dega_scatter_kernel(const GatherArgs a)
     return;
   const uint64_t o0 = a.offsets[c], o1 = a.offsets[c + 1];
   wave_copy_bytes(const_cast<uint8_t *>(a.slabs) + c * a.cap, a.packed + o0, o1 - o0 < a.cap ? o1 - o0 : a.cap, threadIdx.x & 63u);
+}
+
+// =====================================================================================================================
+// Host side: how the kernels above are launched (dega_launch.hpp), for the library and the emulator alike.
+// =====================================================================================================================
+
+// the division magics both coders read: ceil(2^(30+L) / t) for t = 3 .. DIV_TABLE_SIZE - 1, L = ceil(log2 t); the shift
+// L - 2 is recomputed from t (div_shift).  `slack`: zero words behind the table
+inline void build_div_table(std::vector<uint32_t> &tab, size_t slack = 0)
+{
+  tab.assign(DIV_TABLE_SIZE + slack, 0u);
+  for (uint32_t t = 3; t < DIV_TABLE_SIZE; t++)
+  {
+    uint32_t L = 0;
+    while ((1u << L) < t)
+      L++;
+    const unsigned __int128 num = (unsigned __int128)1 << (30 + L);
+    tab[t] = (uint32_t)((num + t - 1) / t);
+  }
+}
+
+// ---- encode ---------------------------------------------------------------------------------------------------------
+struct EncodeVariant
+{
+  bool adaptive;
+  bool narrow;      // valuesize < 32: the samples are masked and range checked against the value size
+  bool w64;         // valuesize 33..64: int64 containers
+  bool f32;         // float32 input, Normalize fused into the fill phase
+  bool counted;     // a ragged batch: a count per channel (float32 input only)
+  bool short_table; // short channels, and enough of them to fill the chip twice: half the table, small rings, two workgroups per CU
+};
+
+// `C`, `T`, `segmented`, `counted`: the launch's own (a chunk's C, not its batch's)
+inline EncodeVariant encode_variant(size_t C, size_t T, bool segmented, bool counted, int valuesize, bool f32, bool adaptive)
+{
+  EncodeVariant v;
+  v.adaptive = adaptive;
+  v.narrow = valuesize < 32;
+  v.w64 = valuesize > 32;
+  v.f32 = f32;
+  v.counted = counted;
+  v.short_table = adaptive && T <= ENC_SHORT_T && !segmented && !counted && valuesize <= 32 && C > 65536;
+  return v;
+}
+
+inline EncodeArgs encode_args(const void *x, size_t C, size_t T, size_t ld, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, const uint32_t *div_magic,
+                              int valuesize, bool big_endian = false, float factor = 0.0f, uint32_t *seg_state = nullptr, uint32_t seg_flags = 0,
+                              const uint64_t *count = nullptr)
+{
+  EncodeArgs a;
+  a.x = reinterpret_cast<const int32_t *>(x);
+  a.C = C;
+  a.T = T;
+  a.ld = ld;
+  a.out = out;
+  a.cap = cap;
+  a.out_bits = out_bits;
+  a.err = err;
+  a.div_magic = div_magic;
+  a.valuesize = (uint32_t)valuesize;
+  a.big_endian = big_endian ? 1u : 0u;
+  a.factor = factor;
+  // the bounds of normalize.c:21, rounded to float by the host compiler exactly as the reference's are
+  a.lo = -(float)((uint64_t)1 << (valuesize - 1));
+  a.hi = (float)(((uint64_t)1 << (valuesize - 1)) - 1);
+  a.seg_state = seg_state;
+  a.seg_flags = seg_flags;
+  a.count = count;
+  return a;
+}
+
+// rows per fill batch and the three rings of a lane (seg bits, the coder's dumps, staged output words)
+struct EncodeRings
+{
+  uint32_t rows, ring, raw, oring;
+};
+constexpr EncodeRings ENC_RINGS_STANDARD{ENC_ROWS, ENC_RING, ENC_RAW, ENC_ORING};
+constexpr EncodeRings ENC_RINGS_W64{4, 32, 16, 32};
+constexpr EncodeRings ENC_RINGS_SHORT{4, 16, 8, 16};
+
+template <typename L>
+inline bool launch(const EncodeVariant &v, const EncodeArgs &a, L &&launch_one)
+{
+  if ((v.narrow && v.w64) || (v.counted && !v.f32) || (v.short_table && (!v.adaptive || v.w64 || v.counted)))
+    return false; // no such instantiation
+  const LaunchGrid grid{(uint32_t)((a.C + ENC_CHANNELS - 1) / ENC_CHANNELS), 1};
+  with_bools(
+      [&](auto ad, auto narrow, auto w64, auto f32, auto counted, auto short_table) {
+        constexpr bool AD = decltype(ad)::value, NARROW = decltype(narrow)::value, W64 = decltype(w64)::value, F32 = decltype(f32)::value,
+                       VAR = decltype(counted)::value, SHORT = decltype(short_table)::value;
+        if constexpr (!(NARROW && W64) && !(VAR && !F32) && !(SHORT && (!AD || W64 || VAR)))
+        {
+          constexpr EncodeRings R = SHORT ? ENC_RINGS_SHORT : (W64 ? ENC_RINGS_W64 : ENC_RINGS_STANDARD);
+          launch_one(dega_encode_kernel<AD, NARROW, R.rows, R.ring, R.raw, R.oring, W64, F32, ENC_PAIRS, SHORT ? ENC_SHORT_TABLE : DIV_TABLE_SIZE, VAR>, grid,
+                     ENC_BLOCK, a);
+        }
+      },
+      v.adaptive, v.narrow, v.w64, v.f32, v.counted, v.short_table);
+  return true;
+}
+
+// ---- decode ---------------------------------------------------------------------------------------------------------
+struct DecodeVariant
+{
+  bool adaptive;
+  bool narrow; // valuesize < 32
+  bool w64;    // valuesize 33..64: int64 containers (float32 rows with f32)
+  bool f32;    // float32 output, Denormalize fused into the row write
+  bool pairs8; // eight pairs of waves per workgroup, the coder staging its own words, in place of four groups of three
+};
+
+constexpr uint32_t DEC_PAIRS8 = 8;
+
+// `batch_C`: the channel count of the whole batch when the launch is one chunk of it; `force_waves`: 0, or the 4 / 8 of
+// DEGA_WAVES_PER_WORKGROUP
+inline DecodeVariant decode_variant(size_t batch_C, int force_waves, int valuesize, bool f32, bool adaptive)
+{
+  DecodeVariant v;
+  v.adaptive = adaptive;
+  v.narrow = valuesize < 32;
+  v.w64 = valuesize > 32;
+  v.f32 = f32;
+  v.pairs8 = !v.w64 && (force_waves == 8 || (force_waves == 0 && batch_C > 65536));
+  return v;
+}
+
+inline DecodeArgs decode_args(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, void *x, uint64_t *out_count, int32_t *err,
+                              const uint32_t *div_magic, int valuesize, bool big_endian = false, float factor = 0.0f, uint32_t *rows_done = nullptr,
+                              uint32_t band_rows = 0)
+{
+  DecodeArgs a;
+  a.in = in;
+  a.cap = cap;
+  a.in_bits = in_bits;
+  a.C = C;
+  a.T = T;
+  a.ld = ld;
+  a.x = reinterpret_cast<int32_t *>(x);
+  a.err = err;
+  a.div_magic = div_magic;
+  a.out_count = out_count;
+  a.valuesize = (uint32_t)valuesize;
+  a.big_endian = big_endian ? 1u : 0u;
+  a.factor = factor;
+  a.rows_done = band_rows != 0 ? rows_done : nullptr;
+  a.band_rows = band_rows;
+  return a;
+}
+
+template <typename L>
+inline bool launch(const DecodeVariant &v, const DecodeArgs &a, L &&launch_one)
+{
+  if (v.w64 && (v.narrow || v.pairs8))
+    return false; // no such instantiation
+  with_bools(
+      [&](auto ad, auto narrow, auto w64, auto f32, auto pairs8) {
+        constexpr bool AD = decltype(ad)::value, NARROW = decltype(narrow)::value, W64 = decltype(w64)::value, F32 = decltype(f32)::value,
+                       P8 = decltype(pairs8)::value;
+        if constexpr (!(W64 && (NARROW || P8)))
+        {
+          constexpr uint32_t PAIRS = P8 ? DEC_PAIRS8 : DEC_PAIRS, CHANNELS = PAIRS * 64, BLOCK_OF = PAIRS * (P8 ? 128 : 192);
+          launch_one(dega_decode_kernel<AD, NARROW, W64, F32, PAIRS, !P8>, LaunchGrid{(uint32_t)((a.C + CHANNELS - 1) / CHANNELS), 1}, BLOCK_OF, a);
+        }
+      },
+      v.adaptive, v.narrow, v.w64, v.f32, v.pairs8);
+  return true;
+}
+
+// ---- normalize, denormalize, synth: one instantiation each -----------------------------------------------------------------
+
+// ranges of rows along y, enough blocks to fill the chip: columns x row-chunks
+inline uint32_t rowsplit_ranges(size_t C, size_t T)
+{
+  const uint32_t gx = (uint32_t)((C + BLOCK - 1) / BLOCK);
+  uint32_t gy = 1;
+  while ((size_t)gx * gy < 2048 && gy < 1024 && (size_t)gy * 64 < T)
+    gy *= 2;
+  return gy;
+}
+
+inline NormalizeArgs normalize_args(const float *v, int32_t *x, size_t C, size_t T, size_t ld, float factor, int32_t *err, int valuesize)
+{
+  // the bounds of normalize.c:21, rounded to float by the host compiler exactly as the reference's are
+  const float lo = -(float)((uint64_t)1 << (valuesize - 1)), hi = (float)(((uint64_t)1 << (valuesize - 1)) - 1);
+  return NormalizeArgs{v, x, C, T, ld, factor, err, lo, hi, valuesize >= 32 ? 0xFFFFFFFFu : (1u << valuesize) - 1u};
+}
+
+inline DenormalizeArgs denormalize_args(const int32_t *x, float *v, size_t C, size_t T, size_t ld, float factor, int valuesize)
+{
+  return DenormalizeArgs{x, v, C, T, ld, factor, (uint32_t)(32 - valuesize)};
+}
+
+// `ranges`: rowsplit_ranges, or what a test forces
+template <typename L>
+inline void launch(const NormalizeArgs &a, uint32_t ranges, L &&launch_one)
+{
+  launch_one(dega_normalize_kernel, LaunchGrid{(uint32_t)((a.C + BLOCK - 1) / BLOCK), ranges}, BLOCK, a);
+}
+
+template <typename L>
+inline void launch(const DenormalizeArgs &a, uint32_t ranges, L &&launch_one)
+{
+  launch_one(dega_denormalize_kernel, LaunchGrid{(uint32_t)((a.C + BLOCK - 1) / BLOCK), ranges}, BLOCK, a);
+}
+
+template <typename L>
+inline void launch(const SynthArgs &a, L &&launch_one)
+{
+  launch_one(dega_synth_kernel, LaunchGrid{(uint32_t)((a.C + BLOCK - 1) / BLOCK), 1}, BLOCK, a);
 }
 
 } // namespace dg

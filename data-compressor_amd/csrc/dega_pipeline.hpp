@@ -743,7 +743,7 @@ static int encode_redo_chunk(dega_hip_ctx *ctx, Pipeline *pl, Slot &sl, const Sh
     sj.C = n; // columns j0 .. j0+n of the chunk's [T][chunk] image; ld stays the image's pitch
     sj.ld = ch.rows_ld;
     int ret;
-    if ((ret = launch_encode(ctx, ch.rows + j0 * sample_bytes(cj), sj, batch_C, (uint8_t *)pl->redo_slabs.p, wc, dm.bits, dm.err, sl.s)) != DEGA_OK)
+    if ((ret = launch_encode(ctx, ch.rows + j0 * sample_bytes(cj), sj, (uint8_t *)pl->redo_slabs.p, wc, dm.bits, dm.err, sl.s)) != DEGA_OK)
       return ret;
     if ((ret = sizes_home(ctx, sl.s, dm, n, pl->redo_hmeta.p)) != DEGA_OK)
       return ret;
@@ -870,7 +870,7 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
       ch.rows = (const uint8_t *)dev_src;
       ch.rows_ld = j.ld;
       cj.ld = j.ld;
-      if ((r = launch_encode(ctx, ch.rows, cj, j.C, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
+      if ((r = launch_encode(ctx, ch.rows, cj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
         return r;
       TRACE("chunk %zu: read in place", k);
     }
@@ -878,14 +878,14 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
     {
       HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.b.p, src, j.ld * esz, j.T * esz, ch.n, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
       if ((r = launch_transpose(ctx, sl.b.p, ch.n, j.T, j.T, esz, nullptr, true, sl.a.p, ch.n, sl.s)) != DEGA_OK ||
-          (r = launch_encode(ctx, sl.a.p, cj, j.C, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
+          (r = launch_encode(ctx, sl.a.p, cj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
         return r;
       TRACE("chunk %zu: channel-major, transposed on the device", k);
     }
     else if (band_rows == 0)
     {
       HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.a.p, src, j.ld * esz, ch.n * esz, j.T, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
-      if ((r = launch_encode(ctx, sl.a.p, cj, j.C, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
+      if ((r = launch_encode(ctx, sl.a.p, cj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
         return r;
     }
     else
@@ -920,7 +920,7 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
         Shape bj = cj;
         bj.T = t1 - t0;
         const uint32_t flags = (b > 0 ? ENC_SEG_CONTINUES : 0u) | (b + 1 < nbands ? ENC_SEG_MORE : 0u);
-        if ((r = launch_encode(ctx, dev_rows, bj, j.C, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s, (uint32_t *)sl.seg_state.p, flags)) != DEGA_OK)
+        if ((r = launch_encode(ctx, dev_rows, bj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s, (uint32_t *)sl.seg_state.p, flags)) != DEGA_OK)
           return r;
       }
       TRACE("chunk %zu: %zu bands of %zu rows, one launch each", k, nbands, band_rows);
@@ -1120,7 +1120,7 @@ static int encode_levels_share(dega_hip_ctx *ctx, const Shape &job, const size_t
     for (size_t k = 0; k < K; k++)
     {
       MetaView dm((uint8_t *)sl.meta.p + k * meta_stride(n), n);
-      if ((r = launch_encode(ctx, ch.lv[k].rows, chunk_shape(lj[k], n), j.C, (uint8_t *)sl.b.p + slab_off, cap[k], dm.bits, dm.err, sl.s)) != DEGA_OK ||
+      if ((r = launch_encode(ctx, ch.lv[k].rows, chunk_shape(lj[k], n), (uint8_t *)sl.b.p + slab_off, cap[k], dm.bits, dm.err, sl.s)) != DEGA_OK ||
           (r = sizes_home(ctx, sl.s, dm, n, nullptr)) != DEGA_OK) // (the K sets go home in one copy, below)
         return r;
       slab_off += n * cap[k];

@@ -1267,4 +1267,23 @@ __global__ void __launch_bounds__(256) lzmh_render_kernel(const RenderArgs a)
   a.err[c] = err;
 }
 
+// ---- host side: how the kernels are launched (dega_launch.hpp); one instantiation each ---------------------------------------
+template <typename L>
+inline void launch(const LzmhEncodeArgs &a, L &&launch_one)
+{
+  launch_one(lzmh_encode_kernel, LaunchGrid{(uint32_t)((a.C + LZ_BLOCK - 1) / LZ_BLOCK), 1}, LZ_ENC_THREADS, a);
+}
+
+template <typename L>
+inline void launch(const LzmhDecodeArgs &a, L &&launch_one)
+{
+  launch_one(lzmh_decode_kernel, LaunchGrid{(uint32_t)((a.C + LZ_BLOCK - 1) / LZ_BLOCK), 1}, LZD_THREADS, a);
+}
+
+template <typename L>
+inline void launch(const RenderArgs &a, L &&launch_one)
+{
+  launch_one(lzmh_render_kernel, LaunchGrid{(uint32_t)((a.C + 255) / 256), 1}, 256u, a);
+}
+
 } // namespace dg

@@ -49,6 +49,7 @@
 #pragma once
 
 #include "dega_intrinsics.hpp"
+#include "dega_launch.hpp"
 
 #include <stddef.h>
 
@@ -231,6 +232,56 @@ __global__ void __launch_bounds__(256) dega_transpose_kernel(const TransposeArgs
     tr_drain<E, VS, true>(a, tile, r0, k0, lane, wave);
   else
     tr_drain<E, VS, false>(a, tile, r0, k0, lane, wave);
+}
+
+// ---- host side: how the kernel is launched (dega_launch.hpp) ----------------------------------------------------------------
+struct TransposeVariant
+{
+  uint32_t elem_bytes; // 4 or 8
+  bool wide_ld;        // 16-byte loads
+  bool wide_st;        // 16-byte stores
+};
+
+// 16-byte loads / stores on each side whose every row starts on a 16-byte boundary (a vector that crosses the edge of the
+// logical region is done by elements in its lane, so the extents do not matter)
+inline TransposeVariant transpose_variant(const void *src, size_t sp, const void *dst, size_t dp, size_t elem_bytes)
+{
+  const size_t V = 16 / elem_bytes;
+  return TransposeVariant{(uint32_t)elem_bytes, ((uintptr_t)src & 15u) == 0 && sp % V == 0, ((uintptr_t)dst & 15u) == 0 && dp % V == 0};
+}
+
+// S[R][sp] -> D[K][dp]; the channel (what `count` is indexed by) is the source row when channel_rows.  The tiles are
+// launch()'s to fill in (tr_plan).
+inline TransposeArgs transpose_args(const void *src, size_t R, size_t K, size_t sp, const uint64_t *count, bool channel_rows, void *dst, size_t dp)
+{
+  TransposeArgs a;
+  a.src = src;
+  a.dst = dst;
+  a.R = R;
+  a.K = K;
+  a.sp = sp;
+  a.dp = dp;
+  a.count = count;
+  a.count_on_rows = channel_rows ? 1u : 0u;
+  a.tiles_k = a.tiles = 0;
+  return a;
+}
+
+// `gx_max`: as tr_plan's
+template <typename L>
+inline bool launch(const TransposeVariant &v, TransposeArgs a, uint64_t gx_max, L &&launch_one)
+{
+  LaunchGrid grid;
+  if ((v.elem_bytes != 4 && v.elem_bytes != 8) || !tr_plan(a.R, a.K, gx_max, a, grid.x, grid.y))
+    return false;
+  with_bools(
+      [&](auto wide_elem, auto wide_ld, auto wide_st) {
+        typedef std::conditional_t<decltype(wide_elem)::value, uint64_t, uint32_t> E;
+        constexpr uint32_t V = 16 / sizeof(E);
+        launch_one(dega_transpose_kernel<E, decltype(wide_ld)::value ? V : 1, decltype(wide_st)::value ? V : 1>, grid, TR_BLOCK, a);
+      },
+      v.elem_bytes == 8, v.wide_ld, v.wide_st);
+  return true;
 }
 
 } // namespace dg

@@ -1,9 +1,9 @@
 // sim_csv_read.cpp -- runs the shipped `decode csv` kernel source (data-compressor_amd/csrc/csv_read_kernels.hpp) under the
-// thread-per-lane emulator of hipsim.hpp.  TEST INFRASTRUCTURE ONLY; see hipsim.hpp.  Built by tests/test_csv_read_host.py
-// (its own g++ step, as sim_csv.cpp has; tests/sim/Makefile stays as it is).
+// thread-per-lane emulator of hipsim.hpp.  TEST INFRASTRUCTURE ONLY; see hipsim.hpp.  Built by the pattern rule of
+// tests/sim/Makefile (libcsv_read_sim.so) for tests/test_csv_read_host.py.
 #define DEGA_SIM 1
 #define dg dgsim // keep the emulated kernels' symbols apart from libdega_hip.so's
-#include "hipsim.hpp"
+#include "sim_launch.hpp"
 
 #include "../../data-compressor_amd/csrc/csv_read_kernels.hpp"
 
@@ -19,20 +19,7 @@ extern "C" __attribute__((visibility("default"))) int sim_csv_read(const uint8_t
   for (size_t c = 0; c < C; c++)
     if (len[c] > stride)
       return -1;
-  CsvReadArgs a;
-  a.text = text;
-  a.stride = stride;
-  a.len = len;
-  a.C = C;
-  a.column = column <= 0xFFFFFFFFu ? (uint32_t)column : 0u;
-  a.sep = (uint32_t)sep;
-  a.v = v;
-  a.max_T = max_T;
-  a.ld = ld;
-  a.out_count = out_count;
-  a.err = err;
-  sim::launch(dega_csv_read_kernel, dim3((unsigned)((C + CSVR_BLOCK - 1) / CSVR_BLOCK)), dim3(CSVR_BLOCK), a);
-  return 0;
+  return launch(csv_read_args(text, stride, len, C, column, sep, v, max_T, ld, out_count, err), OnEmulator{}) ? 0 : -1;
 }
 
 // one field through the kernel's own conversion, without the emulator: the field's float, or -1 when it has 48 characters

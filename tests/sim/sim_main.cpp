@@ -2,27 +2,43 @@
 // TEST INFRASTRUCTURE ONLY; see hipsim.hpp.
 #define DEGA_SIM 1
 #define dg dgsim // keep the emulated kernels' symbols apart from libdega_hip.so's
-#include "hipsim.hpp"
+#include "sim_launch.hpp"
 
-#include "../../data-compressor_amd/csrc/dega_kernels.hpp"
 #include "../../data-compressor_amd/csrc/lzmh_kernels.hpp"
 
 #include <vector>
 
 using namespace dg;
 
-static std::vector<uint32_t> make_table()
+// the variants as bits, for the tests of the library's choosers
+extern "C" __attribute__((visibility("default"))) int sim_encode_variant(size_t C, size_t T, int segmented, int counted, int valuesize, int f32, int adaptive)
 {
-  std::vector<uint32_t> tab(DIV_TABLE_SIZE + 32, 0u); // + the look-ahead of BacEncoder::fetch_magics
-  for (uint32_t t = 3; t < DIV_TABLE_SIZE; t++)
-  {
-    uint32_t L = 0;
-    while ((1u << L) < t)
-      L++;
-    const unsigned __int128 num = (unsigned __int128)1 << (30 + L);
-    tab[t] = (uint32_t)((num + t - 1) / t);
-  }
-  return tab;
+  const EncodeVariant v = encode_variant(C, T, segmented != 0, counted != 0, valuesize, f32 != 0, adaptive != 0);
+  return (v.adaptive ? 1 : 0) | (v.narrow ? 2 : 0) | (v.w64 ? 4 : 0) | (v.f32 ? 8 : 0) | (v.counted ? 16 : 0) | (v.short_table ? 32 : 0);
+}
+
+extern "C" __attribute__((visibility("default"))) int sim_decode_variant(size_t batch_C, int force_waves, int valuesize, int f32, int adaptive)
+{
+  const DecodeVariant v = decode_variant(batch_C, force_waves, valuesize, f32 != 0, adaptive != 0);
+  return (v.adaptive ? 1 : 0) | (v.narrow ? 2 : 0) | (v.w64 ? 4 : 0) | (v.f32 ? 8 : 0) | (v.pairs8 ? 16 : 0);
+}
+
+// x: int32, or float32 / int64 as `f32` and the valuesize say; short_table: 1 forces the short-channel shape on a small batch
+static int run_encode(const void *x, size_t C, size_t T, size_t ld, bool f32, float factor, int adaptive, int valuesize, uint8_t *out, size_t cap, uint64_t *bits,
+                      int32_t *err, uint32_t *seg_state = nullptr, uint32_t seg_flags = 0, bool short_table = false)
+{
+  EncodeVariant v = encode_variant(C, T, seg_state != nullptr, false, valuesize, f32, adaptive != 0);
+  v.short_table = v.short_table || short_table;
+  return launch(v, encode_args(x, C, T, ld, out, cap, bits, err, sim_div_table(), valuesize, false, factor, seg_state, seg_flags), OnEmulator{}) ? 0 : -1;
+}
+
+// pairs8: 1 forces the 8-pair workgroup shape that the library uses for batches of more than 64 Ki channels
+static int run_decode(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, bool f32, float factor, int adaptive, int valuesize,
+                      void *x, uint64_t *counts, int32_t *err, bool pairs8 = false)
+{
+  DecodeVariant v = decode_variant(C, 0, valuesize, f32, adaptive != 0);
+  v.pairs8 = v.pairs8 || pairs8;
+  return launch(v, decode_args(in, cap, in_bits, C, T, ld, x, counts, err, sim_div_table(), valuesize, false, factor), OnEmulator{}) ? 0 : -1;
 }
 
 extern "C" __attribute__((visibility("default"))) void sim_set_drag(int from_wave, int microseconds)
@@ -33,21 +49,7 @@ extern "C" __attribute__((visibility("default"))) void sim_set_drag(int from_wav
 
 extern "C" __attribute__((visibility("default"))) int sim_encode_vs(const int32_t *x, size_t C, size_t T, size_t ld, int adaptive, int valuesize, uint8_t *out, size_t cap, uint64_t *bits, int32_t *err)
 {
-  static const std::vector<uint32_t> tab = make_table();
-  EncodeArgs a{x, C, T, ld, out, cap, bits, err, tab.data(), (uint32_t)valuesize};
-  const dim3 grid((unsigned)((C + ENC_CHANNELS - 1) / ENC_CHANNELS));
-  if (valuesize < 32)
-  {
-    if (adaptive)
-      sim::launch(dega_encode_kernel<true, true>, grid, dim3(ENC_BLOCK), a);
-    else
-      sim::launch(dega_encode_kernel<false, true>, grid, dim3(ENC_BLOCK), a);
-  }
-  else if (adaptive)
-    sim::launch(dega_encode_kernel<true>, grid, dim3(ENC_BLOCK), a);
-  else
-    sim::launch(dega_encode_kernel<false>, grid, dim3(ENC_BLOCK), a);
-  return 0;
+  return run_encode(x, C, T, ld, false, 0.0f, adaptive, valuesize, out, cap, bits, err);
 }
 
 extern "C" __attribute__((visibility("default"))) int sim_encode(const int32_t *x, size_t C, size_t T, size_t ld, int adaptive, uint8_t *out, size_t cap, uint64_t *bits, int32_t *err)
@@ -57,21 +59,7 @@ extern "C" __attribute__((visibility("default"))) int sim_encode(const int32_t *
 
 extern "C" __attribute__((visibility("default"))) int sim_decode_var_vs(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, int adaptive, int valuesize, int32_t *x, uint64_t *counts, int32_t *err)
 {
-  static const std::vector<uint32_t> tab = make_table();
-  DecodeArgs a{in, cap, in_bits, C, T, ld, x, err, tab.data(), counts, (uint32_t)valuesize};
-  const dim3 grid((unsigned)((C + DEC_CHANNELS - 1) / DEC_CHANNELS));
-  if (valuesize < 32)
-  {
-    if (adaptive)
-      sim::launch(dega_decode_kernel<true, true>, grid, dim3(DEC_BLOCK), a);
-    else
-      sim::launch(dega_decode_kernel<false, true>, grid, dim3(DEC_BLOCK), a);
-  }
-  else if (adaptive)
-    sim::launch(dega_decode_kernel<true>, grid, dim3(DEC_BLOCK), a);
-  else
-    sim::launch(dega_decode_kernel<false>, grid, dim3(DEC_BLOCK), a);
-  return 0;
+  return run_decode(in, cap, in_bits, C, T, ld, false, 0.0f, adaptive, valuesize, x, counts, err);
 }
 
 extern "C" __attribute__((visibility("default"))) int sim_decode_vs(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, int adaptive, int valuesize, int32_t *x, int32_t *err)
@@ -86,22 +74,20 @@ extern "C" __attribute__((visibility("default"))) int sim_decode(const uint8_t *
 
 extern "C" __attribute__((visibility("default"))) int sim_normalize(const float *v, size_t C, size_t T, size_t ld, float factor, int32_t *x, int32_t *err)
 {
-  NormalizeArgs a{v, x, C, T, ld, factor, err, -2147483648.0f, 2147483648.0f, 0xFFFFFFFFu};
-  sim::launch(dega_normalize_kernel, dim3((unsigned)((C + BLOCK - 1) / BLOCK), 2), dim3(BLOCK), a);
+  launch(normalize_args(v, x, C, T, ld, factor, err, 32), 2, OnEmulator{});
   return 0;
 }
 
 extern "C" __attribute__((visibility("default"))) int sim_denormalize(const int32_t *x, size_t C, size_t T, size_t ld, float factor, float *v)
 {
-  DenormalizeArgs a{x, v, C, T, ld, factor, 0u};
-  sim::launch(dega_denormalize_kernel, dim3((unsigned)((C + BLOCK - 1) / BLOCK), 2), dim3(BLOCK), a);
+  launch(denormalize_args(x, v, C, T, ld, factor, 32), 2, OnEmulator{});
   return 0;
 }
 
 extern "C" __attribute__((visibility("default"))) int sim_synth(int32_t *x, size_t C, size_t T, size_t ld, uint64_t seed, uint64_t c0, uint32_t S)
 {
   SynthArgs a{x, C, T, ld, seed, c0, S};
-  sim::launch(dega_synth_kernel, dim3((unsigned)((C + BLOCK - 1) / BLOCK)), dim3(BLOCK), a);
+  launch(a, OnEmulator{});
   return 0;
 }
 
@@ -110,19 +96,11 @@ extern "C" __attribute__((visibility("default"))) int sim_synth(int32_t *x, size
 extern "C" __attribute__((visibility("default"))) int sim_encode_segments(const int32_t *x, size_t C, size_t T, size_t ld, int adaptive, const size_t *cuts, int ncuts, uint8_t *out,
                                                                        size_t cap, uint64_t *bits, int32_t *err)
 {
-  static const std::vector<uint32_t> tab = make_table();
   std::vector<uint32_t> state(ENC_STATE_WORDS * C, 0xDEADBEEFu);
-  const dim3 grid((unsigned)((C + ENC_CHANNELS - 1) / ENC_CHANNELS));
   for (int k = 0; k + 1 < ncuts; k++)
-  {
-    EncodeArgs a{x + cuts[k] * ld, C, cuts[k + 1] - cuts[k], ld, out, cap, bits, err, tab.data(), 32u};
-    a.seg_state = state.data();
-    a.seg_flags = (k > 0 ? ENC_SEG_CONTINUES : 0u) | (k + 2 < ncuts ? ENC_SEG_MORE : 0u);
-    if (adaptive)
-      sim::launch(dega_encode_kernel<true>, grid, dim3(ENC_BLOCK), a);
-    else
-      sim::launch(dega_encode_kernel<false>, grid, dim3(ENC_BLOCK), a);
-  }
+    if (run_encode(x + cuts[k] * ld, C, cuts[k + 1] - cuts[k], ld, false, 0.0f, adaptive, 32, out, cap, bits, err, state.data(),
+                   (k > 0 ? ENC_SEG_CONTINUES : 0u) | (k + 2 < ncuts ? ENC_SEG_MORE : 0u)) != 0)
+      return -1;
   (void)T;
   return 0;
 }
@@ -136,7 +114,7 @@ extern "C" __attribute__((visibility("default"))) int sim_encode_segments(const 
 template <bool ADAPTIVE>
 static int fast_vs_slow(uint64_t seed, int rounds, int *word_taken, int *ripples)
 {
-  static const std::vector<uint32_t> tab = make_table();
+  const uint32_t *const tab = sim_div_table();
   std::mt19937_64 rng(seed);
   int bad = 0;
   constexpr uint32_t RAWT = 128; // a raw "ring" that holds everything a word can produce: the writer runs afterwards
@@ -200,7 +178,7 @@ static int fast_vs_slow(uint64_t seed, int rounds, int *word_taken, int *ripples
       word = ~word;
     // (a) bit at a time
     for (uint32_t i = 0; i < 32; i++)
-      e.encode_bit((word >> (31u - i)) & 1u, tab.data());
+      e.encode_bit((word >> (31u - i)) & 1u, tab);
     e.end_bits_word();
     // (b) the word path of the lane's class -- or, two rounds out of three, of a more general class, as happens when
     //     another lane of the wave needs one
@@ -222,8 +200,8 @@ static int fast_vs_slow(uint64_t seed, int rounds, int *word_taken, int *ripples
         for (int part = 0; part < 2; part++)
         {
           uint32_t Mg[32];
-          f.fetch_magics_first(tab.data(), Mg);
-          f.template encode_word<false, 8, true>(word, tab.data(), Mg);
+          f.fetch_magics_first(tab, Mg);
+          f.template encode_word<false, 8, true>(word, tab, Mg);
           if (f.after_part(word))
             break;
         }
@@ -232,20 +210,20 @@ static int fast_vs_slow(uint64_t seed, int rounds, int *word_taken, int *ripples
     else if (cls == CLS_BITS)
     {
       for (uint32_t i = 0; i < 32; i++)
-        f.encode_bit((word >> (31u - i)) & 1u, tab.data());
+        f.encode_bit((word >> (31u - i)) & 1u, tab);
       f.end_bits_word();
     }
     else
     {
       (*word_taken)++;
       uint32_t Mg[32];
-      f.fetch_magics_first(tab.data(), Mg);
+      f.fetch_magics_first(tab, Mg);
       if (cls == CLS_FAST8)
-        f.template encode_word<false, 8>(word, tab.data(), Mg);
+        f.template encode_word<false, 8>(word, tab, Mg);
       else if (cls == CLS_FAST4)
-        f.template encode_word<false, 4>(word, tab.data(), Mg);
+        f.template encode_word<false, 4>(word, tab, Mg);
       else if constexpr (ADAPTIVE)
-        f.template encode_word<true, 4>(word, tab.data(), Mg);
+        f.template encode_word<true, 4>(word, tab, Mg);
     }
     // the writers absorb what the two coders dumped; a carry past the held-back word ripples into the stored words
     const uint32_t before_a = buf_a[we.pos >= 2 ? we.pos - 2 : 0], before_b = before_a;
@@ -296,21 +274,21 @@ extern "C" __attribute__((visibility("default"))) int sim_fast_vs_slow(uint64_t 
 extern "C" __attribute__((visibility("default"))) int sim_lzmh_encode(const uint8_t *in, size_t stride, const uint64_t *in_len, size_t C, uint8_t *out, size_t cap, uint64_t *bits, int32_t *err)
 {
   LzmhEncodeArgs a{in, stride, in_len, C, out, cap, bits, err};
-  sim::launch(lzmh_encode_kernel, dim3((unsigned)((C + LZ_BLOCK - 1) / LZ_BLOCK)), dim3(LZ_ENC_THREADS), a);
+  launch(a, OnEmulator{});
   return 0;
 }
 
 extern "C" __attribute__((visibility("default"))) int sim_lzmh_render(const int32_t *x, size_t C, size_t T, size_t ld, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err)
 {
   RenderArgs a{x, C, T, ld, out, stride, out_len, err};
-  sim::launch(lzmh_render_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), a);
+  launch(a, OnEmulator{});
   return 0;
 }
 
 extern "C" __attribute__((visibility("default"))) int sim_lzmh_decode(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err)
 {
   LzmhDecodeArgs a{in, cap, in_bits, C, out, stride, out_len, err};
-  sim::launch(lzmh_decode_kernel, dim3((unsigned)((C + LZ_BLOCK - 1) / LZ_BLOCK)), dim3(LZD_THREADS), a);
+  launch(a, OnEmulator{});
   return 0;
 }
 
@@ -318,14 +296,7 @@ extern "C" __attribute__((visibility("default"))) int sim_lzmh_decode(const uint
 // (counts: NULL, or up to T samples per channel and the count reported, as sim_decode_var_vs)
 extern "C" __attribute__((visibility("default"))) int sim_decode_wide_var(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, int adaptive, int32_t *x, uint64_t *counts, int32_t *err)
 {
-  static const std::vector<uint32_t> tab = make_table();
-  DecodeArgs a{in, cap, in_bits, C, T, ld, x, err, tab.data(), counts, 32u};
-  const dim3 grid((unsigned)((C + 511) / 512)); // 8 pairs of waves, 16-sample ring
-  if (adaptive)
-    sim::launch(dega_decode_kernel<true, false, false, false, 8, false>, grid, dim3(1024), a);
-  else
-    sim::launch(dega_decode_kernel<false, false, false, false, 8, false>, grid, dim3(1024), a);
-  return 0;
+  return run_decode(in, cap, in_bits, C, T, ld, false, 0.0f, adaptive, 32, x, counts, err, true);
 }
 
 extern "C" __attribute__((visibility("default"))) int sim_decode_wide(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, int adaptive, int32_t *x, int32_t *err)
@@ -336,32 +307,35 @@ extern "C" __attribute__((visibility("default"))) int sim_decode_wide(const uint
 // valuesize 33..64: int64 containers
 extern "C" __attribute__((visibility("default"))) int sim_encode64(const int64_t *x, size_t C, size_t T, size_t ld, int adaptive, int valuesize, uint8_t *out, size_t cap, uint64_t *bits, int32_t *err)
 {
-  static const std::vector<uint32_t> tab = make_table();
-  EncodeArgs a{reinterpret_cast<const int32_t *>(x), C, T, ld, out, cap, bits, err, tab.data(), (uint32_t)valuesize};
-  const dim3 grid((unsigned)((C + ENC_CHANNELS - 1) / ENC_CHANNELS));
-  if (adaptive)
-    sim::launch(dega_encode_kernel<true, false, 4, 32, 16, 32, true>, grid, dim3(ENC_BLOCK), a);
-  else
-    sim::launch(dega_encode_kernel<false, false, 4, 32, 16, 32, true>, grid, dim3(ENC_BLOCK), a);
-  return 0;
+  return run_encode(x, C, T, ld, false, 0.0f, adaptive, valuesize, out, cap, bits, err);
 }
 
 extern "C" __attribute__((visibility("default"))) int sim_decode64(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, int adaptive, int valuesize, int64_t *x, uint64_t *counts, int32_t *err)
 {
-  static const std::vector<uint32_t> tab = make_table();
-  DecodeArgs a{in, cap, in_bits, C, T, ld, reinterpret_cast<int32_t *>(x), err, tab.data(), counts, (uint32_t)valuesize};
-  const dim3 grid((unsigned)((C + DEC_CHANNELS - 1) / DEC_CHANNELS));
-  if (adaptive)
-    sim::launch(dega_decode_kernel<true, false, true>, grid, dim3(DEC_BLOCK), a);
-  else
-    sim::launch(dega_decode_kernel<false, false, true>, grid, dim3(DEC_BLOCK), a);
-  return 0;
+  return run_decode(in, cap, in_bits, C, T, ld, false, 0.0f, adaptive, valuesize, x, counts, err);
 }
 
 // the half-filled-wave launch the library uses for up to 64 Ki channels
 extern "C" __attribute__((visibility("default"))) int sim_lzmh_decode_half(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err)
 {
   LzmhDecodeArgs a{in, cap, in_bits, C, out, stride, out_len, err};
-  sim::launch(lzmh_decode_kernel, dim3((unsigned)((C + LZ_BLOCK - 1) / LZ_BLOCK)), dim3(LZD_THREADS), a); // (one shape since the pairs of waves)
+  launch(a, OnEmulator{});
   return 0;
+}
+
+// the short-channel shape that the library uses for more than 64 Ki channels of at most 124 samples, forced on a small batch
+extern "C" __attribute__((visibility("default"))) int sim_encode_short(const int32_t *x, size_t C, size_t T, size_t ld, int adaptive, int valuesize, uint8_t *out, size_t cap, uint64_t *bits, int32_t *err)
+{
+  return run_encode(x, C, T, ld, false, 0.0f, adaptive, valuesize, out, cap, bits, err, nullptr, 0, true);
+}
+
+// the float entries (Normalize / Denormalize fused into the coders), valuesize 1..64
+extern "C" __attribute__((visibility("default"))) int sim_encode_f32(const float *v, size_t C, size_t T, size_t ld, float factor, int adaptive, int valuesize, uint8_t *out, size_t cap, uint64_t *bits, int32_t *err)
+{
+  return run_encode(v, C, T, ld, true, factor, adaptive, valuesize, out, cap, bits, err);
+}
+
+extern "C" __attribute__((visibility("default"))) int sim_decode_f32(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, float factor, int adaptive, int valuesize, float *v, uint64_t *counts, int32_t *err)
+{
+  return run_decode(in, cap, in_bits, C, T, ld, true, factor, adaptive, valuesize, v, counts, err);
 }

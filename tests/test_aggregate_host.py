@@ -16,10 +16,10 @@ from oracle import orc
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from agg_common import same_floats, sequential  # noqa: E402
+from sim_build import sim_library  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "data-compressor_amd", "host")
-SIM_DIR = os.path.join(ROOT, "tests", "sim")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 CLI = os.path.join(HOST, "dccli_amd")
 
@@ -133,10 +133,7 @@ def test_cli_refuses_to_decode_gaggregate(hostlib, tmp_path):
 
 @pytest.fixture(scope="module")
 def sim():
-    so = os.path.join(SIM_DIR, "libagg_sim.so")
-    subprocess.run(["g++", "-std=c++20", "-O2", "-g", "-fPIC", "-shared", "-pthread", "-fvisibility=hidden", "-Wl,-Bsymbolic", "-ffp-contract=off",
-                    "-Wall", "-Wextra", "-Wno-unused-parameter", "-Wno-unknown-pragmas", os.path.join(SIM_DIR, "sim_aggregate.cpp"), "-o", so], check=True)
-    S = C.CDLL(so)
+    S = sim_library("aggregate")
     S.sim_aggregate.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t]
     return S
 

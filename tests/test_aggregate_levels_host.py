@@ -7,7 +7,6 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -18,9 +17,9 @@ from __graft_entry__ import load_package
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from agg_common import same_floats, sequential  # noqa: E402
 from agg_levels_common import Fixture  # noqa: E402
+from sim_build import sim_library  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM_DIR = os.path.join(ROOT, "tests", "sim")
 
 NEW_SYMBOLS = ("dega_hip_aggregate_levels_plan", "dega_hip_aggregate_levels_dev", "dega_hip_encode_levels_f32_dev", "dega_hip_encode_levels_job_host",
                "dega_hip_group_encode_levels")
@@ -155,11 +154,7 @@ def test_plan_refuses_bad_level_lists(dca):
 
 @pytest.fixture(scope="module")
 def sim():
-    so = os.path.join(SIM_DIR, "libagg_levels_sim.so")
-    subprocess.run(["g++", "-std=c++20", "-O2", "-g", "-fPIC", "-shared", "-pthread", "-fvisibility=hidden", "-Wl,-Bsymbolic", "-ffp-contract=off",
-                    "-Wall", "-Wextra", "-Wno-unused-parameter", "-Wno-unknown-pragmas", os.path.join(SIM_DIR, "sim_aggregate_levels.cpp"), "-o", so],
-                   check=True)
-    S = C.CDLL(so)
+    S = sim_library("aggregate_levels")
     S.sim_aggregate_levels.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t]
     return S
 

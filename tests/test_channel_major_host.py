@@ -14,15 +14,17 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 from __graft_entry__ import load_package
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from sim_build import sim_library  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM_DIR = os.path.join(ROOT, "tests", "sim")
 NEW_SYMBOLS = ("dega_hip_to_time_major_dev", "dega_hip_to_channel_major_dev")
 SHAPES = ((1, 1), (63, 65), (64, 64), (65, 63), (130, 257))  # (C, T)
 DTYPES = {4: np.uint32, 8: np.uint64}
@@ -100,10 +102,7 @@ def test_layout_assertions_need_no_gpu(dca):
 
 @pytest.fixture(scope="module")
 def sim():
-    so = os.path.join(SIM_DIR, "libtranspose_sim.so")
-    subprocess.run(["g++", "-std=c++20", "-O2", "-g", "-fPIC", "-shared", "-pthread", "-fvisibility=hidden", "-Wl,-Bsymbolic", "-Wall", "-Wextra",
-                    "-Wno-unused-parameter", "-Wno-unknown-pragmas", os.path.join(SIM_DIR, "sim_transpose.cpp"), "-o", so], check=True)
-    S = C.CDLL(so)
+    S = sim_library("transpose")
     Z, P = C.c_size_t, C.c_void_p
     S.sim_transpose.argtypes = [P, Z, Z, Z, Z, P, C.c_int, P, Z, C.c_int, C.c_int, Z]
     return S

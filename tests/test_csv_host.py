@@ -6,7 +6,6 @@ text comparison is exact bytes and exact lengths.  The parity tests proper are t
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -17,9 +16,9 @@ from __graft_entry__ import load_package
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from agg_common import sequential  # noqa: E402
 from csv_common import DECIMALS, SLACK, Fixture, arrange, check_channels, input_series, input_txt, py_lines  # noqa: E402
+from sim_build import sim_library  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM_DIR = os.path.join(ROOT, "tests", "sim")
 
 NEW_SYMBOLS = ("dega_hip_csv_line_max", "dega_hip_csv_worst_case_bytes", "dega_hip_csv_write_dev", "dega_hip_csv_write_host",
                "dega_hip_lzmh_encode_f32_dev", "dega_hip_lzmh_encode_levels_f32_dev")
@@ -96,10 +95,7 @@ def test_null_context_is_rejected(dca):
 
 @pytest.fixture(scope="module")
 def sim():
-    so = os.path.join(SIM_DIR, "libcsv_sim.so")
-    subprocess.run(["g++", "-std=c++20", "-O2", "-g", "-fPIC", "-shared", "-pthread", "-fvisibility=hidden", "-Wl,-Bsymbolic", "-ffp-contract=off",
-                    "-Wall", "-Wextra", "-Wno-unused-parameter", "-Wno-unknown-pragmas", os.path.join(SIM_DIR, "sim_csv.cpp"), "-o", so], check=True)
-    S = C.CDLL(so)
+    S = sim_library("csv")
     S.sim_csv.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                           C.c_int]
     return S

@@ -7,7 +7,6 @@ have it, which are a separate, counted set.  The parity tests proper are tests/t
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -18,9 +17,9 @@ from __graft_entry__ import load_package
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import csv_read_common as crc  # noqa: E402
 from csv_common import Fixture, input_series  # noqa: E402
+from sim_build import sim_library  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM_DIR = os.path.join(ROOT, "tests", "sim")
 NEW_SYMBOLS = ("dega_hip_csv_read_dev", "dega_hip_csv_read_host", "dega_hip_lzmh_decode_f32_dev")
 FILLER = 0x7FC12345  # what the columns beyond C hold: no call may touch it
 PER_CLASS = 100000
@@ -72,10 +71,7 @@ def test_null_context_is_rejected(dca):
 
 @pytest.fixture(scope="module")
 def sim():
-    so = os.path.join(SIM_DIR, "libcsv_read_sim.so")
-    subprocess.run(["g++", "-std=c++20", "-O2", "-g", "-fPIC", "-shared", "-pthread", "-fvisibility=hidden", "-Wl,-Bsymbolic", "-ffp-contract=off",
-                    "-Wall", "-Wextra", "-Wno-unused-parameter", "-Wno-unknown-pragmas", os.path.join(SIM_DIR, "sim_csv_read.cpp"), "-o", so], check=True)
-    S = C.CDLL(so)
+    S = sim_library("csv_read")
     S.sim_csv_read.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
     S.sim_csv_read_field.restype = C.c_int64
     S.sim_csv_read_field.argtypes = [C.c_char_p, C.c_size_t]

@@ -195,3 +195,75 @@ def test_channels_coded_over_several_launches_with_saved_state(sim):
             for c in np.nonzero(ok)[0]:
                 nb = (int(want_bits[c]) + 7) // 8
                 assert out[c, :nb].tobytes() == want_out[c, :nb].tobytes(), (ad, cuts, c)
+
+
+def test_library_choosers_pick_the_short_table_and_the_eight_pairs(sim):
+    """The library's own choosers (encode_variant / decode_variant at the foot of dega_kernels.hpp), each condition on both
+    sides of its boundary.  The variant comes back as bits: adaptive 1, narrow 2, 64-bit 4, float32 8, then counted 16 and
+    short table 32 (encode) or eight pairs 16 (decode)."""
+    Z, I = C.c_size_t, C.c_int
+    sim.sim_encode_variant.argtypes = [Z, Z, I, I, I, I, I]
+    sim.sim_decode_variant.argtypes = [Z, I, I, I, I]
+
+    def enc(Cn=65537, T=124, segmented=0, counted=0, vs=32, f32=0, ad=1):
+        return sim.sim_encode_variant(Cn, T, segmented, counted, vs, f32, ad)
+    SHORT = 32
+    assert enc() == 1 | SHORT and enc(vs=31) == 1 | 2 | SHORT and enc(f32=1) == 1 | 8 | SHORT and enc(vs=1, T=0, Cn=1 << 30) == 1 | 2 | SHORT
+    assert enc(Cn=65536) == 1 and enc(T=125) == 1  # the launch's channels and samples, one below / above
+    assert enc(segmented=1) == 1 and enc(ad=0) == 0
+    assert enc(counted=1, f32=1) == 1 | 8 | 16 and enc(vs=33) == 1 | 4 and enc(vs=33, f32=1, counted=1, ad=0) == 4 | 8 | 16
+    assert enc(Cn=320, T=130, vs=17, f32=1, ad=0) == 2 | 8
+
+    def dec(batch=320, force=0, vs=32, f32=0, ad=1):
+        return sim.sim_decode_variant(batch, force, vs, f32, ad)
+    PAIRS8 = 16
+    assert dec(batch=65536) == 1 and dec(batch=65537) == 1 | PAIRS8
+    assert dec(force=8) == 1 | PAIRS8 and dec(force=8, vs=9, f32=1, ad=0) == 2 | 8 | PAIRS8
+    assert dec(batch=1 << 30, force=4) == 1 and dec(batch=65537, force=4, vs=31) == 1 | 2
+    for batch in (320, 65537, 1 << 30):  # never for 64-bit containers
+        for force in (0, 4, 8):
+            assert dec(batch, force, vs=33) == 1 | 4 and dec(batch, force, vs=64, f32=1, ad=0) == 4 | 8
+
+
+def chain_encode(x_uint, vs, ad):
+    """the oracle's diff -> seg -> bac over valuesize-bit unsigned samples, one channel: (status, bytes, bits)"""
+    v = np.asarray(x_uint, dtype=np.uint64)
+    b = np.zeros(len(v) * vs, dtype=np.uint8)
+    for k in range(vs):
+        b[k::vs] = (v >> np.uint64(vs - 1 - k)) & np.uint64(1)
+    data, n, r = np.packbits(b).tobytes(), len(v) * vs, 0
+    for name in ("diff", "seg", "bac"):
+        r, data, n = orc.stage(name, True, data, n, valuesize=vs, adaptive=ad)
+        if r != 0:
+            break
+    return r, data, n
+
+
+@pytest.mark.parametrize("vs", (32, 17))
+@pytest.mark.parametrize("T", (124, 1))
+def test_short_table_encoder_forced_on_a_small_batch(sim, T, vs):
+    """The short-channel encode shape (half the division table in LDS, small rings: what the library takes for more than
+    64 Ki channels of at most 124 samples) forced on 320 channels -- two workgroups, the second partial.  Noise of
+    valuesize - 1 bits costs the most symbols a sample can; at T = 124 a channel counts up to the last table entry the
+    shape holds (124 * 65 + 2 + 68 words of fetch-ahead <= 8 192).  The streams are the oracle's and the standard shape's."""
+    sig = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    sim.sim_encode_short.argtypes = sig
+    sim.sim_encode_vs.argtypes = sig
+    Cn = 320
+    x = np.random.default_rng(77 + T + vs).integers(0, 1 << (vs - 1), (T, Cn), dtype=np.int64).astype(np.int32)
+    cap = 4 * ((T * 12 + 67) // 4)
+    got = []
+    for fn in (sim.sim_encode_short, sim.sim_encode_vs):
+        out = np.zeros((Cn, cap), dtype=np.uint8)
+        bits = np.zeros(Cn, dtype=np.uint64)
+        err = np.full(Cn, 99, dtype=np.int32)
+        assert fn(x.ctypes.data, Cn, T, Cn, 1, vs, out.ctypes.data, cap, bits.ctypes.data, err.ctypes.data) == 0
+        got.append((out, bits, err))
+    for out, bits, err in got:
+        assert (err == 0).all()
+        for c in range(Cn):
+            r, data, n = chain_encode(x[:, c], vs, 1)
+            assert r == 0 and int(bits[c]) == n and out[c, : (n + 7) // 8].tobytes() == data[: (n + 7) // 8], (T, vs, c)
+    assert (got[0][1] == got[1][1]).all() and (got[0][0] == got[1][0]).all()
+    # the shape exists for the adaptive model only: no kernel to force it on otherwise
+    assert sim.sim_encode_short(x.ctypes.data, Cn, T, Cn, 0, vs, got[0][0].ctypes.data, cap, got[0][1].ctypes.data, got[0][2].ctypes.data) == -1

@@ -11,7 +11,6 @@ dega_hip_encode_segment_dev), so no test can reach that line."""
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -23,9 +22,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from agg_common import same_floats, sequential  # noqa: E402
 from ragged_common import (CASES, FACTOR, HONEST, LEVELS, POISON, SETS, Fixture, poisoned, same_rows, same_streams, same_texts,  # noqa: E402
                            untouched)
+from sim_build import sim_library  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM_DIR = os.path.join(ROOT, "tests", "sim")
 NEW_SYMBOLS = ("dega_hip_aggregate_levels_var_dev", "dega_hip_encode_f32_var_dev", "dega_hip_encode_levels_f32_var_dev", "dega_hip_csv_write_var_dev",
                "dega_hip_lzmh_encode_levels_f32_var_dev")
 SENTINEL = np.float32(-12345.0)
@@ -141,10 +140,7 @@ def test_fixture_shape_and_the_one_honest_error(fx):
 
 @pytest.fixture(scope="module")
 def sim():
-    so = os.path.join(SIM_DIR, "libragged_sim.so")
-    subprocess.run(["g++", "-std=c++20", "-O2", "-g", "-fPIC", "-shared", "-pthread", "-fvisibility=hidden", "-Wl,-Bsymbolic", "-ffp-contract=off",
-                    "-Wall", "-Wextra", "-Wno-unused-parameter", "-Wno-unknown-pragmas", os.path.join(SIM_DIR, "sim_ragged.cpp"), "-o", so], check=True)
-    S = C.CDLL(so)
+    S = sim_library("ragged")
     Z, P = C.c_size_t, C.c_void_p
     S.sim_aggregate_var.argtypes = [P, Z, Z, Z, P, P, Z, P, P, P, P, C.c_int, Z]
     S.sim_csv_var.argtypes = [P, Z, Z, Z, P, C.c_uint, Z, C.c_int, P, Z, P, P, C.c_int]

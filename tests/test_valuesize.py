@@ -423,3 +423,194 @@ def test_gpu_valuesize_above_32(gold64):
     with pytest.raises(dca.DegaError):
         ctx.encode64_host(np.zeros((4, 4), dtype=np.int64), 32)  # 1..32 live in the int32 entry points
     ctx.close()
+
+
+# ---- the float entries: Normalize / Denormalize fused into the coders --------------------------------------------------------
+FLOAT_C, FLOAT_T, FLOAT_FACTOR = 320, 130, 100.0  # two workgroups, the second partial; a last partial batch of rows
+
+
+def float_chain(col, vs, ad, factor=FLOAT_FACTOR):
+    """One channel through the oracle's normalize -> diff -> seg -> bac and back: (status, stream bytes, bits, decoded float32)"""
+    col = np.ascontiguousarray(col, dtype=np.float32)
+    data, n, r = col.tobytes(), col.size * 32, 0
+    for name in ("normalize", "diff", "seg", "bac"):
+        r, data, n = orc.stage(name, True, data, n, valuesize=vs, adaptive=ad, factor=factor)
+        if r != 0:
+            return r, b"", 0, None
+    back, bn = data, n
+    for name in ("bac", "seg", "diff", "normalize"):
+        r, back, bn = orc.stage(name, False, back, bn, valuesize=vs, adaptive=ad, factor=factor)
+        assert r == 0
+    return 0, data[: (n + 7) // 8], n, np.frombuffer(back[: bn // 8], dtype=np.float32)
+
+
+def float_walks(vs, Cn=FLOAT_C, T=FLOAT_T, seed=40):
+    """Walks that stay inside the value size (|v| * factor below 2^(valuesize - 1)) and stay positive, so that no difference
+    leaves it either (diff.c:15-18)."""
+    lim = float(1 << (vs - 1)) / FLOAT_FACTOR
+    rng = np.random.default_rng(seed + vs)
+    return np.ascontiguousarray((lim / 4 + np.cumsum(rng.uniform(-lim / 2000, lim / 2000, (T, Cn)), axis=0)).astype(np.float32)), lim
+
+
+_FLOAT_REFERENCE = {}
+
+
+def float_reference(vs, ad):
+    """The batch of the float tests at this value size and what the oracle makes of it, computed once: (v, err [C], bits [C],
+    streams (list of bytes), back float32 [T, C]).  Beside the walks: channels that leave the range of normalize.c:21 on
+    either side or at once, the bounds themselves, values that round to 0."""
+    if (vs, ad) not in _FLOAT_REFERENCE:
+        v, lim = float_walks(vs)
+        v[50:, 3] = lim * 1.5      # above the range from row 50 on
+        v[0, 7] = -lim * 1.01      # below it at once
+        v[:, 300] = lim * 0.999    # just inside, on the last workgroup
+        v[:, 301] = -lim           # the lower bound itself is inside (normalize.c:21)
+        v[::2, 11] = 0.004         # rounds to 0
+        err = np.zeros(FLOAT_C, dtype=np.int32)
+        bits = np.zeros(FLOAT_C, dtype=np.uint64)
+        back = np.zeros(v.shape, dtype=np.float32)
+        streams = []
+        for c in range(FLOAT_C):
+            r, data, n, b = float_chain(v[:, c], vs, ad)
+            err[c], bits[c] = r, n
+            streams.append(data)
+            if r == 0:
+                back[:, c] = b
+        assert 2 <= int((err != 0).sum()) <= 8  # the range check is exercised, and most channels are coded
+        _FLOAT_REFERENCE[(vs, ad)] = (v, err, bits, streams, back)
+    return _FLOAT_REFERENCE[(vs, ad)]
+
+
+def float_cap(T, vs):
+    return 4 * ((T * (2 * vs + 3) // 4 + 64) // 4 + 4)  # (bytes: room for the static model's log2(3) bits per seg bit)
+
+
+def check_float_streams(want, out, bits, err, what):
+    _, w_err, w_bits, w_streams, _ = want
+    assert (np.asarray(err) == w_err).all(), what
+    for c in np.nonzero(w_err == 0)[0]:
+        assert int(bits[c]) == int(w_bits[c]) and bytes(out[c][: len(w_streams[c])]) == w_streams[c], (what, int(c))
+
+
+def float_slabs(want, cap):
+    """the oracle's streams as the decoders take them; channels in error get an empty stream (and are not looked at)"""
+    _, w_err, w_bits, w_streams, _ = want
+    slabs = np.zeros((len(w_streams), cap), dtype=np.uint8)
+    for c, st in enumerate(w_streams):
+        slabs[c, : len(st)] = np.frombuffer(st, dtype=np.uint8)
+    return slabs, np.where(w_err == 0, w_bits, 0).astype(np.uint64)
+
+
+def check_float_back(want, back, derr, what):
+    _, w_err, _, _, w_back = want
+    ok = w_err == 0
+    assert (np.asarray(derr)[ok] == 0).all(), what
+    assert np.ascontiguousarray(np.asarray(back)[:, ok]).tobytes() == np.ascontiguousarray(w_back[:, ok]).tobytes(), what
+
+
+@pytest.mark.parametrize("ad", (1, 0))
+@pytest.mark.parametrize("vs", (32, 17, 40))
+def test_kernel_logic_float_entries_without_counts(sim, vs, ad):
+    """dega_hip_encode_f32_dev / dega_hip_decode_f32_dev as the library launches them (variant, arguments -- the bounds of
+    normalize.c:21 among them -- and grid from the library's own code), 320 channels x 130 samples: status, stream and
+    decoded floats are the oracle's normalize -> diff -> seg -> bac chain's, byte for byte."""
+    Z, P, I = C.c_size_t, C.c_void_p, C.c_int
+    sim.sim_encode_f32.argtypes = [P, Z, Z, Z, C.c_float, I, I, P, Z, P, P]
+    sim.sim_decode_f32.argtypes = [P, Z, P, Z, Z, Z, C.c_float, I, I, P, P, P]
+    want = float_reference(vs, ad)
+    v, Cn, T, cap = want[0], FLOAT_C, FLOAT_T, float_cap(FLOAT_T, vs)
+    out = np.zeros((Cn, cap), dtype=np.uint8)
+    bits = np.zeros(Cn, dtype=np.uint64)
+    err = np.full(Cn, 99, dtype=np.int32)
+    assert sim.sim_encode_f32(v.ctypes.data, Cn, T, Cn, FLOAT_FACTOR, ad, vs, out.ctypes.data, cap, bits.ctypes.data, err.ctypes.data) == 0
+    check_float_streams(want, out, bits, err, (vs, ad))
+    slabs, sbits = float_slabs(want, cap)
+    back = np.zeros((T, Cn), dtype=np.float32)
+    counts = np.zeros(Cn, dtype=np.uint64)
+    derr = np.full(Cn, 99, dtype=np.int32)
+    assert sim.sim_decode_f32(slabs.ctypes.data, cap, sbits.ctypes.data, Cn, T, Cn, FLOAT_FACTOR, ad, vs, back.ctypes.data, counts.ctypes.data, derr.ctypes.data) == 0
+    assert (counts[want[1] == 0] == T).all()
+    check_float_back(want, back, derr, (vs, ad))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("vs", (17, 40))
+def test_gpu_float_entries_static_model_at_other_value_sizes(vs):
+    """The static model's float kernels below and above 32 bits (the adaptive ones are held to the reference's fixture by
+    test_fused_float_entry_against_the_reference): the uniform encode and decode, and the counted encode."""
+    import torch
+    from __graft_entry__ import load_package
+    dca = load_package()
+    ctx = dca.Context(0)
+    want = float_reference(vs, 0)
+    v, T, Cn, cap = want[0], FLOAT_T, FLOAT_C, float_cap(FLOAT_T, vs)
+    vd = torch.from_numpy(v).cuda()
+    out, bits, err = ctx.encode_f32(vd, FLOAT_FACTOR, 0, cap=cap, valuesize=vs)
+    torch.cuda.synchronize()
+    check_float_streams(want, out.cpu().numpy(), bits.cpu().numpy(), err.cpu().numpy(), ("encode_f32", vs))
+    slabs, sbits = float_slabs(want, cap)
+    back, derr = ctx.decode_f32(torch.from_numpy(slabs).cuda(), torch.from_numpy(sbits.astype(np.int64)).cuda(), T, FLOAT_FACTOR, 0, valuesize=vs)
+    torch.cuda.synchronize()
+    check_float_back(want, back.cpu().numpy(), derr.cpu().numpy(), ("decode_f32", vs))
+    # counted: channel c is its first count[c] rows (1 .. T, both ends among them)
+    walks, _ = float_walks(vs)
+    count = np.random.default_rng(vs).integers(1, T + 1, Cn)
+    count[:2], count[-2:] = (1, T), (T, 1)
+    out, bits, err, _ = ctx.encode_f32(torch.from_numpy(walks).cuda(), FLOAT_FACTOR, 0, cap=cap, valuesize=vs, count=torch.from_numpy(count.astype(np.int64)).cuda())
+    torch.cuda.synchronize()
+    out, bits, err = out.cpu().numpy(), bits.cpu().numpy(), err.cpu().numpy()
+    for c in range(Cn):
+        r, data, n, _ = float_chain(walks[: count[c], c], vs, 0)
+        assert r == 0 == int(err[c]) and int(bits[c]) == n and out[c, : len(data)].tobytes() == data, ("counted", vs, c)
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_eight_pair_decoders_on_a_small_batch(monkeypatch):
+    """DEGA_WAVES_PER_WORKGROUP=8 on a fresh context: the workgroups of eight pairs of waves that decode batches of more than
+    64 Ki channels, at 320 channels -- the float exits (both models, 32 bits and narrow) and the static model's int32 one;
+    the streams are the oracle's, and so is what comes back."""
+    import torch
+    from __graft_entry__ import load_package
+    dca = load_package()
+    monkeypatch.setenv("DEGA_WAVES_PER_WORKGROUP", "8")
+    ctx = dca.Context(0)
+    T, Cn = FLOAT_T, FLOAT_C
+    for vs in (32, 17):
+        for ad in (1, 0):
+            want = float_reference(vs, ad)
+            slabs, sbits = float_slabs(want, float_cap(T, vs))
+            back, derr = ctx.decode_f32(torch.from_numpy(slabs).cuda(), torch.from_numpy(sbits.astype(np.int64)).cuda(), T, FLOAT_FACTOR, ad, valuesize=vs)
+            torch.cuda.synchronize()
+            check_float_back(want, back.cpu().numpy(), derr.cpu().numpy(), ("decode_f32, eight pairs", vs, ad))
+    x = (np.cumsum(np.random.default_rng(8).integers(-300, 301, (T, Cn)), axis=0) + 70000).astype(np.int32)
+    out, bits, err = orc.encode_batch_tc(x, 0)
+    assert (err == 0).all()
+    out = np.ascontiguousarray(np.pad(out, ((0, 0), (0, -out.shape[1] % 4))))
+    y, derr = ctx.decode_host(out, bits, T, adaptive=0)
+    assert (derr == 0).all() and (y == x).all()
+    ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("vs", (32, 17))
+def test_gpu_float_entry_takes_the_short_table_shape(vs):
+    """More than 64 Ki channels of at most 124 samples take the short-channel encode shape (half the division table in LDS),
+    its float instantiations with the float entry: a sample of channels against the oracle's chain.  (No smaller batch
+    reaches these kernels: the shape is chosen by the launch's channel count.)"""
+    import torch
+    from __graft_entry__ import load_package
+    dca = load_package()
+    ctx = dca.Context(0)
+    Cn, T = 65536 + 320, 40
+    v, _ = float_walks(vs, Cn, T, seed=3)
+    out, bits, err = ctx.encode_f32(torch.from_numpy(v).cuda(), FLOAT_FACTOR, 1, cap=float_cap(T, vs), valuesize=vs)
+    torch.cuda.synchronize()
+    assert int((err != 0).sum()) == 0
+    sel = np.concatenate([np.arange(0, Cn, 997), np.arange(Cn - 70, Cn)])
+    selt = torch.from_numpy(sel).cuda()
+    oh, bh = out[selt].cpu().numpy(), bits[selt].cpu().numpy()
+    for i, c in enumerate(sel):
+        r, data, n, _ = float_chain(v[:, c], vs, 1)
+        assert r == 0 and int(bh[i]) == n and oh[i, : len(data)].tobytes() == data, (vs, int(c))
+    ctx.close()
