@@ -1146,6 +1146,14 @@ static bool aligned16(const void *p)
   return ((uintptr_t)p & 15u) == 0;
 }
 
+// When does a channel fit its slab?  With F the full 32-bit words of its stream and W = 4 * ceil(bits / 32) its bytes in whole
+// words, lzmh_coding_wave stores F / 4 blocks of 16 bytes, the k-th at byte 16 * k and only if 16 * k + 32 <= cap, and then,
+// in finish, the F % 4 words left and the partial one, only if 4 * (F + 1) <= cap.  16 * (F / 4) <= 4 * F <= W, so
+//   W + 16 <= cap   is SUFFICIENT: the last block passes (16 * (F / 4 - 1) + 32 <= W + 16) and so does finish (4 * F + 4 <= W + 4);
+//   W > cap         always fails in finish (W is 4 * F or 4 * F + 4): ERROR_MEMORY, out_bits 0;
+// in between either happens, by F % 4.  dega_hip_lzmh_worst_case_bytes(n) >= ceil(10 * n / 8) + 32 >= W + 29 satisfies the
+// sufficient condition for every text of n bytes (no code spends more than 10 bits on a byte).  tests/lzmh_encoder_common.py
+// (check_slab_end) holds the kernel to exactly this, with a canary behind every slab.
 extern "C" int dega_hip_lzmh_encode_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t stride, const uint64_t *in_len, size_t C, uint8_t *out,
                                         size_t cap, uint64_t *out_bits, int32_t *err, void *stream)
 {

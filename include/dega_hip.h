@@ -191,8 +191,13 @@ int dega_hip_synth_dev(dega_hip_ctx *ctx, int32_t *x_tc, size_t C, size_t T, siz
    per channel and bit for bit, including the codec's quirks (an input of exactly 403 bytes encodes to nothing, :161-174;
    the decoder stops once its code register is empty after the last input bit, :571).  One GPU lane per channel.
    encode: in = uint8 [C][stride] (device, 16-byte aligned, stride a multiple of 16), in_len[c] <= stride bytes of channel c;
-           out = uint8 [C][cap] slabs of 32-bit big-endian words (cap a multiple of 16, >= dega_hip_lzmh_worst_case_bytes(n)
+           out = uint8 [C][cap] slabs of 32-bit big-endian words (cap a multiple of 16, >= 48; >= dega_hip_lzmh_worst_case_bytes(n)
            never overflows), out_bits[c] = exact bit length, err[c] = 0 | ERROR_MEMORY (slab too small) | ERROR_INVALID_VALUE.
+           When a slab is too small: a channel is coded whenever its stream, rounded up to whole 32-bit words, and 16 bytes
+           more fit cap (dega_hip_lzmh_worst_case_bytes leaves 32); it reports ERROR_MEMORY and out_bits 0 whenever the
+           rounded stream does not fit cap; in between either, and a status of 0 always comes with the whole stream.  Nothing
+           is written outside a channel's slab, nor, when it is coded, behind its stream's last word; what a channel that
+           reports ERROR_MEMORY leaves in its slab is unspecified.  Bytes behind in_len[c] are read but change nothing.
    decode: the inverse: in/cap/in_bits as produced by encode (cap a multiple of 4), out = uint8 [C][stride] (stride a
            multiple of 8), out_len[c] = decoded bytes; ERROR_MEMORY when a channel does not fit its row.
    render: the synthetic LZMH workload of SURVEY.md 8(d): int32 channels [T][ld] (centi-units) as ASCII "%d.%02d\n" lines. */
