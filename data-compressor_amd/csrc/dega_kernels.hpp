@@ -30,7 +30,12 @@ namespace dg
 {
 
 // lo = -(float)2^(valuesize-1), hi = (float)(2^(valuesize-1) - 1) as the host's C compiler rounds them (normalize.c:21;
-// hi rounds up to 2^(valuesize-1) from valuesize 26 on), mask = the low valuesize bits written (normalize.c:24)
+// hi rounds up to 2^(valuesize-1) from valuesize 26 on), mask = the low valuesize bits written (normalize.c:24).
+// Only a float in [-2^31, 2^31) is converted -- the conversion of any other is undefined in C++, and the host's and the
+// GPU's convert instructions answer it differently.  Two such floats pass :21: exactly 2^31 at valuesize 32, whose int64
+// has the low bits 0x80000000, and a NaN, which fails no comparison and which the reference's conversion (cvttss2si with a
+// 64-bit destination) turns into 0x8000000000000000, low bits 0.  Everything else out there was rejected: its integer is
+// not looked at, and is 0.
 DG_DEV bool normalize_value(float v, float factor, int32_t &out, float lo = -2147483648.0f, float hi = 2147483648.0f, uint32_t mask = 0xFFFFFFFFu)
 {
   if (v > 0.0f)
@@ -38,7 +43,9 @@ DG_DEV bool normalize_value(float v, float factor, int32_t &out, float lo = -214
   else if (v < 0.0f)
     v = fadd_once(fmul_once(v, factor), -0.5f); // :19-20
   const bool ok = !(v < lo || v > hi); // :21 -- for valuesize 32 (float)(2^31-1) is 2^31, so exactly 2^31 passes
-  out = (int32_t)((v >= 2147483648.0f ? 0x80000000u : (uint32_t)(int32_t)v) & mask); // :23-24 (int64) truncation, low valuesize bits
+  const bool converts = v >= -2147483648.0f && v < 2147483648.0f; // (false for a NaN)
+  const uint32_t n = converts ? (uint32_t)(int32_t)v : (v >= 2147483648.0f ? 0x80000000u : 0u); // :23-24 (int64) truncation, low valuesize bits
+  out = (int32_t)(n & mask);
   return ok;
 }
 
@@ -945,7 +952,9 @@ DG_DEV void decode_coding_wave(const DecodeArgs &a, const uint32_t *tab, uint32_
   const uint64_t nbits = live ? a.in_bits[c] : 0;
   StreamTail tail;
   tail.init(nbits, cap_words);
-  const uint32_t max_seg_bits = (uint32_t)a.T * 65u; // no valid stream of T samples decodes to more bits (T <= 2^25)
+  // no valid stream of T samples decodes to more bits (T <= 2^25): a codeword has at most min(valuesize, 63) prefix zeros
+  // (seg.c:55-56,74), so 65 bits up to valuesize 32 and up to 127 above
+  const uint32_t max_seg_bits = (uint32_t)a.T * (a.valuesize > 32u ? 2u * (a.valuesize < 63u ? a.valuesize : 63u) + 1u : 65u);
   const uint64_t bp_limit = nbits + 14u;             // at most 14 phantom bits after the stream's end (bac.c:171-186)
   // 16 bytes per lane and DMA instruction when the slabs allow it (a lane's words are 16-byte aligned, and a group of
   // four never leaves the slab); else four single words

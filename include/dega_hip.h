@@ -167,7 +167,10 @@ int dega_hip_decode64_var_host(dega_hip_ctx *ctx, const uint8_t *in, size_t cap,
                                int adaptive, int valuesize, int64_t *x_tc, uint64_t *out_count, int32_t *err);
 
 /* ---- float entry / exit (normalize.c), device pointers ----------------------------------------------------------- */
-/* v: float32 [T][ld] -> x: int32 [T][ld]; err[c] = DEGA_ERROR_INVALID_VALUE if any sample of channel c fails the range check. */
+/* v: float32 [T][ld] -> x: int32 [T][ld]; err[c] = DEGA_ERROR_INVALID_VALUE if any sample of channel c fails the range check.
+   A NaN fails no comparison of that check and is a value like any other, as in the reference: the field 0 (at valuesize 64,
+   through the fused entry below, 0x8000000000000000 -- what the reference's conversion gives).  Infinities are out of
+   range.  Subnormal readings, products and quotients are IEEE: kept, not flushed. */
 int dega_hip_normalize_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, float factor, int valuesize,
                            int32_t *x_tc, int32_t *err, void *stream);
 int dega_hip_denormalize_dev(dega_hip_ctx *ctx, const int32_t *x_tc, size_t C, size_t T, size_t ld, float factor, int valuesize,
@@ -223,7 +226,8 @@ int dega_hip_group_lzmh_decode(dega_hip_group *group, const uint8_t *packed, con
 
 /* ---- float entry / exit fused into the coder kernels, device pointers ----------------------------------- */
 /* v_tc: float32 [T][ld].  One launch: Normalize on each value as it enters the fill phase (normalize.c:16-24; a value
-   failing the range check of :21 gives that channel DEGA_ERROR_INVALID_VALUE), then diff -> seg -> bac as above.  No int32
+   failing the range check of :21 gives that channel DEGA_ERROR_INVALID_VALUE; a NaN passes it and is coded as the field 0,
+   at valuesize 64 as 0x8000000000000000), then diff -> seg -> bac as above.  No int32
    intermediate exists in HBM.  valuesize 1..64.  decode: Denormalize (:36-38) in the row write; out_count NULL = exactly
    T samples per channel, else up to T and the counts are reported. */
 int dega_hip_encode_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, float factor, int adaptive, int valuesize,

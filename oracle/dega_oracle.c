@@ -170,7 +170,13 @@ static int normalize_one(float value, float factor, unsigned valuesize, int64_t 
   }
   if (value < (-(float)((uint64_t)1 << (valuesize - 1))) || value > (float)(((uint64_t)1 << (valuesize - 1)) - 1)) /* :21 */
     return ORC_ERROR_INVALID_VALUE;
-  *out = (int64_t)value; /* :23 truncation toward zero */
+  /* :23 truncation toward zero.  A NaN passes both comparisons of :21, and 2^63 passes at value size 64 (the upper bound
+     rounds up to it): the reference's cvttss2si answers both with the "integer indefinite" 0x8000000000000000, whose low
+     bits are 0 below 64 bits.  Said here in so many words: the C conversion of such a float is undefined. */
+  if (value != value || value >= 9223372036854775808.0f)
+    *out = INT64_MIN;
+  else
+    *out = (int64_t)value;
   return ORC_NO_ERROR;
 }
 
@@ -219,6 +225,26 @@ int orc_normalize_decode(const orc_bits_t *in, orc_bits_t *out, float factor, un
         return ret;
   }
   return ORC_NO_ERROR;
+}
+
+/* The two directions value by value, each with a verdict of its own (a stage call ends at the first value out of range):
+   status[i] = what normalize.c:21-22 returns for v[i] alone, out[i] = the low `valuesize` bits written (0 with an error). */
+void orc_normalize_each(const float *v, size_t n, float factor, unsigned valuesize, uint64_t *out, int32_t *status)
+{
+  size_t i;
+  for (i = 0; i < n; i++)
+  {
+    int64_t x = 0;
+    status[i] = normalize_one(v[i], factor, valuesize, &x);
+    out[i] = status[i] != ORC_NO_ERROR ? 0 : (valuesize == 64 ? (uint64_t)x : (uint64_t)x & (((uint64_t)1 << valuesize) - 1));
+  }
+}
+
+void orc_denormalize_each(const uint64_t *u, size_t n, float factor, unsigned valuesize, float *out)
+{
+  size_t i;
+  for (i = 0; i < n; i++)
+    out[i] = (float)sign_extend(u[i], valuesize) / factor; /* normalize.c:37-38 */
 }
 
 /* ------------------------------------------------------------------------------------------------------------------

@@ -51,6 +51,8 @@ size_t orc_bits_nbytes(const orc_bits_t *b); /* bytes a file would hold: ceil(nb
    Return ORC_NO_ERROR or a negative code, like the reference's enc_dec_function_t (DCLib/inc/enc_dec.h:11). */
 int orc_normalize_encode(const orc_bits_t *in, orc_bits_t *out, float factor, unsigned valuesize); /* normalize.c:9-27 */
 int orc_normalize_decode(const orc_bits_t *in, orc_bits_t *out, float factor, unsigned valuesize); /* normalize.c:29-41 */
+void orc_normalize_each(const float *v, size_t n, float factor, unsigned valuesize, uint64_t *out, int32_t *status); /* :16-24 per value */
+void orc_denormalize_each(const uint64_t *u, size_t n, float factor, unsigned valuesize, float *out);               /* :36-38 per value */
 int orc_diff_encode(const orc_bits_t *in, orc_bits_t *out, unsigned valuesize);                    /* diff.c:9-23 */
 int orc_diff_decode(const orc_bits_t *in, orc_bits_t *out, unsigned valuesize);                    /* diff.c:25-37 */
 int orc_seg_encode(const orc_bits_t *in, orc_bits_t *out, unsigned valuesize);                     /* seg.c:31-43 */

@@ -53,6 +53,10 @@ def lib():
         L.orc_dega_decode_batch_tc.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
         for name in ("orc_normalize_encode", "orc_normalize_decode"):
             getattr(L, name).argtypes = [C.POINTER(_Bits), C.POINTER(_Bits), C.c_float, C.c_uint]
+        L.orc_normalize_each.restype = None
+        L.orc_normalize_each.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_uint, C.c_void_p, C.c_void_p]
+        L.orc_denormalize_each.restype = None
+        L.orc_denormalize_each.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_uint, C.c_void_p]
         for name in ("orc_diff_encode", "orc_diff_decode", "orc_seg_encode", "orc_seg_decode"):
             getattr(L, name).argtypes = [C.POINTER(_Bits), C.POINTER(_Bits), C.c_uint]
         for name in ("orc_lzmh_encode", "orc_lzmh_decode"):
@@ -122,6 +126,23 @@ def stage(name, encode, data, nbits, valuesize=32, adaptive=0, factor=100.0):
     if name == "lzmh":
         return _stage(fn, data, nbits)
     return _stage(fn, data, nbits, C.c_uint(valuesize))
+
+
+def normalize_each(v, factor, valuesize):
+    """normalize.c:16-24 for every float32 of v alone: (status int32 [n], the low `valuesize` bits written uint64 [n])"""
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    out = np.zeros(v.size, dtype=np.uint64)
+    status = np.zeros(v.size, dtype=np.int32)
+    lib().orc_normalize_each(v.ctypes.data, v.size, factor, valuesize, out.ctypes.data, status.ctypes.data)
+    return status, out
+
+
+def denormalize_each(u, factor, valuesize):
+    """normalize.c:36-38 for every `valuesize`-bit field of u (uint64): float32 [n]"""
+    u = np.ascontiguousarray(u, dtype=np.uint64)
+    out = np.zeros(u.size, dtype=np.float32)
+    lib().orc_denormalize_each(u.ctypes.data, u.size, factor, valuesize, out.ctypes.data)
+    return out
 
 
 def file_bytes(data, nbits):

@@ -72,16 +72,27 @@ extern "C" __attribute__((visibility("default"))) int sim_decode(const uint8_t *
   return sim_decode_var_vs(in, cap, in_bits, C, T, ld, adaptive, 32, x, nullptr, err);
 }
 
+// the standalone float entry and exit, valuesize 1..32 (the arguments, the bounds of normalize.c:21 among them, from the library's own code)
+extern "C" __attribute__((visibility("default"))) int sim_normalize_vs(const float *v, size_t C, size_t T, size_t ld, float factor, int valuesize, int32_t *x, int32_t *err)
+{
+  launch(normalize_args(v, x, C, T, ld, factor, err, valuesize), T > 1 ? 2 : 1, OnEmulator{});
+  return 0;
+}
+
+extern "C" __attribute__((visibility("default"))) int sim_denormalize_vs(const int32_t *x, size_t C, size_t T, size_t ld, float factor, int valuesize, float *v)
+{
+  launch(denormalize_args(x, v, C, T, ld, factor, valuesize), T > 1 ? 2 : 1, OnEmulator{});
+  return 0;
+}
+
 extern "C" __attribute__((visibility("default"))) int sim_normalize(const float *v, size_t C, size_t T, size_t ld, float factor, int32_t *x, int32_t *err)
 {
-  launch(normalize_args(v, x, C, T, ld, factor, err, 32), 2, OnEmulator{});
-  return 0;
+  return sim_normalize_vs(v, C, T, ld, factor, 32, x, err);
 }
 
 extern "C" __attribute__((visibility("default"))) int sim_denormalize(const int32_t *x, size_t C, size_t T, size_t ld, float factor, float *v)
 {
-  launch(denormalize_args(x, v, C, T, ld, factor, 32), 2, OnEmulator{});
-  return 0;
+  return sim_denormalize_vs(x, C, T, ld, factor, 32, v);
 }
 
 extern "C" __attribute__((visibility("default"))) int sim_synth(int32_t *x, size_t C, size_t T, size_t ld, uint64_t seed, uint64_t c0, uint32_t S)
@@ -338,4 +349,16 @@ extern "C" __attribute__((visibility("default"))) int sim_encode_f32(const float
 extern "C" __attribute__((visibility("default"))) int sim_decode_f32(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, float factor, int adaptive, int valuesize, float *v, uint64_t *counts, int32_t *err)
 {
   return run_decode(in, cap, in_bits, C, T, ld, true, factor, adaptive, valuesize, v, counts, err);
+}
+
+// the float entry in the short-channel shape (adaptive model, valuesize 1..32) and the float exit in the 8-pair workgroup shape
+// (valuesize 1..32), forced on a small batch as sim_encode_short and sim_decode_wide force them
+extern "C" __attribute__((visibility("default"))) int sim_encode_f32_short(const float *v, size_t C, size_t T, size_t ld, float factor, int valuesize, uint8_t *out, size_t cap, uint64_t *bits, int32_t *err)
+{
+  return run_encode(v, C, T, ld, true, factor, 1, valuesize, out, cap, bits, err, nullptr, 0, true);
+}
+
+extern "C" __attribute__((visibility("default"))) int sim_decode_f32_wide(const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld, float factor, int adaptive, int valuesize, float *v, uint64_t *counts, int32_t *err)
+{
+  return run_decode(in, cap, in_bits, C, T, ld, true, factor, adaptive, valuesize, v, counts, err, true);
 }
