@@ -166,6 +166,11 @@ DG_DEV void load_div_table(uint32_t *tab, const uint32_t *gtab, uint64_t symbols
 #ifndef DG_ENC_CODE_PRIO
 #define DG_ENC_CODE_PRIO 3
 #endif
+// A step of the coding wave with lanes that have no word queued takes the masked steady path for all 64 lanes, the dry
+// ones coding an empty part (1), or the general route under an exec mask (0)
+#ifndef DG_ENC_DRY_LANES
+#define DG_ENC_DRY_LANES 1
+#endif
 #ifndef DG_DEC_PARSE_SLEEP
 #define DG_DEC_PARSE_SLEEP 6
 #endif
@@ -605,6 +610,9 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
 }
 
 // ---- the coding wave -------------------------------------------------------------------------------------------------
+#if defined(DEGA_SIM)
+inline uint64_t sim_enc_steps[6]; // the emulator's count of the coding waves' passes by kind (DG_COUNT below)
+#endif
 template <bool ADAPTIVE, uint32_t RING, uint32_t RAW>
 DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const uint32_t *ring_col, uint32_t *raw_col, uint32_t *pub_mine, const uint32_t *pub_peer,
                                const uint32_t *pub_writer, uint32_t lane, size_t c, bool live)
@@ -630,10 +638,18 @@ DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const u
   enc.classify(); // the class of the first word
   wave_priority<DG_ENC_CODE_PRIO>();
   bool waiting = false; // (wave uniform) at low priority, nothing to do
+  // what the coding wave's passes were: 0 steady / 1 steady masked / 2 other word paths / 3 nothing to do (no word, no room) /
+  // 4 steady masked with a dry lane (a lane without a word, coding an empty part) / 5, the emulator only: those of 2 that
+  // took a fast word path under an exec mask for no other reason than a dry lane
 #if defined(DEGA_DIAG) && (DEGA_DIAG & 32) && !defined(DEGA_SIM)
-  // diagnostic build: what the coding wave's passes were (steady / steady masked / other word paths / nothing to do: no word, no room), in cycles too
-  uint64_t dg_n[4] = {0, 0, 0, 0}, dg_c[4] = {0, 0, 0, 0}, dg_t = __builtin_amdgcn_s_memtime();
+  // diagnostic build: counted per wave, in cycles too
+  uint64_t dg_n[5] = {0, 0, 0, 0, 0}, dg_c[5] = {0, 0, 0, 0, 0}, dg_t = __builtin_amdgcn_s_memtime();
 #define DG_COUNT(k) do { const uint64_t now_ = __builtin_amdgcn_s_memtime(); dg_n[k]++; dg_c[k] += now_ - dg_t; dg_t = now_; } while (0)
+#define DG_COUNTING 1
+#elif defined(DEGA_SIM)
+  // the emulator: counted over all waves since the last reset (tests/sim/sim_dry_lanes.cpp: sim_encode_step_counts)
+#define DG_COUNT(k) do { if (lane == 0) __atomic_fetch_add(&sim_enc_steps[k], 1, __ATOMIC_RELAXED); } while (0)
+#define DG_COUNTING 1
 #else
 #define DG_COUNT(k)
 #endif
@@ -677,6 +693,44 @@ DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const u
     }
     // The same with some lanes at a halving of the counts or a change of the division shift (CLS_SPLIT: the word in two
     // parts, see BacCoder): the masked fast path for all 64 lanes -- whole words for the others
+#if DG_ENC_DRY_LANES
+    // ... and with dry lanes: the filler works in row lockstep and the lanes' bit rates differ, so a lane below the wave's
+    // highest rate has no word queued now and then (a lane past its last word never has, nor has a lane without a
+    // channel).  Such a lane codes the empty part -- no symbol, no count, its four entries hold no bits -- and the wave
+    // keeps to straight-line code.  Every lane needs room for the four entries and a fast class, the dry ones too: theirs
+    // keeps the fetch of the division magics inside the table.
+    {
+      if (wave_all(room4 && enc.cls <= CLS_SPLIT) && wave_any(has))
+      {
+        if (waiting)
+        {
+          wave_priority<DG_ENC_CODE_PRIO>();
+          waiting = false;
+        }
+#if defined(DG_COUNTING)
+        const bool dry_step = wave_any(!has);
+#endif
+        enc.template encode_word<false, 8, true>(word, tab, Mg, !has);
+        const bool whole = has && (enc.cls != CLS_SPLIT || enc.after_part(word));
+        rd += whole ? 1u : 0u;
+        enc.safe -= has && enc.safe != 0u ? 1u : 0u;
+        const bool again = whole && enc.safe == 0u;
+        if (wave_any(again))
+        {
+          if (again)
+            enc.classify();
+        }
+        peer_store(pub_mine, (rd & 0xFFFFu) | ((enc.rwr & 0xFFu) << 16));
+#if defined(DG_COUNTING)
+        if (dry_step)
+          DG_COUNT(4);
+        else
+          DG_COUNT(1);
+#endif
+        continue;
+      }
+    }
+#else
     if constexpr (ADAPTIVE)
     {
       if (wave_all(ready && enc.cls <= CLS_SPLIT))
@@ -701,6 +755,7 @@ DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const u
         continue;
       }
     }
+#endif
     // (the slower word paths write eight entries; the bit path waits for room by itself).  A lane with a word but no room
     // for its entries holds the whole wave up: the writer never waits for this wave, so room comes, and the lanes stay in
     // step -- a wave whose lanes take turns needs more steps, each with its exec masks and merges
@@ -726,6 +781,9 @@ DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const u
       wave_priority<DG_ENC_CODE_PRIO>();
       waiting = false;
     }
+#if defined(DEGA_SIM)
+    const bool dry_only = wave_all(room4 && enc.cls <= CLS_SPLIT); // but for its lanes without a word this step were a steady one
+#endif
     // Which word path?  The wave takes the most expensive class among its lanes.
     uint32_t cls = can ? enc.cls : CLS_FAST8;
     bool act = can; // lanes that code (a part of) a word in this step
@@ -789,6 +847,10 @@ DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const u
     }
     peer_store(pub_mine, (rd & 0xFFFFu) | ((enc.rwr & 0xFFu) << 16));
     DG_COUNT(2);
+#if defined(DEGA_SIM)
+    if (dry_only)
+      DG_COUNT(5);
+#endif
   }
 
   if (live)
@@ -813,8 +875,8 @@ DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const u
   }
   peer_store(pub_mine, (rd & 0xFFFFu) | ((enc.rwr & 0xFFu) << 16) | ENC_PUB_DONE | (peer & ENC_PUB_BAD));
 #if defined(DEGA_DIAG) && (DEGA_DIAG & 32) && !defined(DEGA_SIM)
-  if (live && lane < 8) // (the writer of a diagnostic build leaves out_bits alone)
-    a.out_bits[c] = lane < 4 ? dg_n[lane] : dg_c[lane - 4];
+  if (live && lane < 10) // (the writer of a diagnostic build leaves out_bits alone)
+    a.out_bits[c] = lane < 5 ? dg_n[lane] : dg_c[lane - 5];
 #endif
 }
 

@@ -370,15 +370,18 @@ struct BacCoder
   //                  counts change only by c1 -= lps.
   // GENERAL = true : the whole model update of bac.c:54-81 by selects; magics read from the table as the counts move.
   // DUMP: symbols between two dumps (8 or 4): 32 / DUMP raw entries, for which the caller has made sure of room.
-  // MASKED: only the symbols part_lo .. part_hi are coded, the others are no-ops (CLS_SPLIT; fast path only).
+  // MASKED: only the symbols part_lo .. part_hi are coded, the others are no-ops (CLS_SPLIT; fast path only).  `empty`
+  //         (MASKED only): the lane has no word -- it codes the empty part: 32 no-ops, four entries of binary 10, counts
+  //         and interval as they were.  (Its magics are fetched like any other lane's and masked away: a lane of a fast
+  //         class has tot + 32 <= MAX_FREQUENCY, a lane without a word is never in the middle of one, part_lo = 0.)
   template <bool GENERAL, uint32_t DUMP, bool MASKED = false>
-  DG_DEV void encode_word(uint32_t word, const uint32_t *magic, uint32_t (&Mg)[32])
+  DG_DEV void encode_word(uint32_t word, const uint32_t *magic, uint32_t (&Mg)[32], bool empty = false)
   {
     static_assert(!GENERAL || ADAPTIVE, "the static model never needs the general path");
-    static_assert(!MASKED || (!GENERAL && ADAPTIVE), "parts of words are a matter of the adaptive fast path");
+    static_assert(!MASKED || !GENERAL, "parts of words are a matter of the fast path");
     uint32_t mm = 0u - mps;                          // all ones when the MPS is the bit value 1
     // symbol i <-> bit 31 - i; a symbol that is not coded becomes a more probable one with magic 0
-    const uint32_t active = MASKED ? (0xFFFFFFFFu >> part_lo) & (0xFFFFFFFFu << (31u - part_hi)) : 0xFFFFFFFFu;
+    const uint32_t active = MASKED ? (empty ? 0u : (0xFFFFFFFFu >> part_lo) & (0xFFFFFFFFu << (31u - part_hi))) : 0xFFFFFFFFu;
     const uint32_t lw = GENERAL ? word : ((word ^ mm) & active); // fast: bit set = less probable symbol (the MPS cannot change)
     const uint32_t sh_word = div_shift(tot);
     const uint32_t tot_word = tot - (MASKED ? part_lo : 0u);
@@ -470,7 +473,7 @@ struct BacCoder
     if (GENERAL)
       mps = mm & 1u;
     else if (ADAPTIVE)
-      tot += MASKED ? part_hi - part_lo + 1u : 32u;
+      tot += MASKED ? (empty ? 0u : part_hi - part_lo + 1u) : 32u;
   }
 };
 
