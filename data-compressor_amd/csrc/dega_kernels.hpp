@@ -1,9 +1,9 @@
 // dega_kernels.hpp -- the HIP kernels of the DEGA path for gfx950 (MI355X).
 //
-// Mapping: one lane = one meter channel, one wave = 64 adjacent channels; a workgroup = 4 (or 8) PAIRS of waves sharing
-// the 64 KiB table of division magics in LDS -- of each pair one wave does the serial arithmetic, its partner on the same
-// SIMD the work around it (see the encode and decode kernels).  Samples are [T][ld] (time-major), so a wave's row read is
-// one coalesced 256-byte segment and every input byte is fetched exactly once.
+// Mapping: one lane = one meter channel, one wave = 64 adjacent channels; a workgroup = 4 GROUPS of three waves (the wide
+// decoder: 8 pairs) sharing the 64 KiB table of division magics in LDS -- of each group one wave does the serial
+// arithmetic, its partners on the same SIMD the work around it (see the encode and decode kernels).  Samples are [T][ld]
+// (time-major), so a wave's row read is one coalesced 256-byte segment and every input byte is fetched exactly once.
 //
 // Encode (diff -> seg -> bac fused, nothing but the final stream ever goes back to HBM):
 //   filling wave (row lockstep)   every lane takes the same rows t..t+7, forms the delta, its signed exp-Golomb codeword
@@ -73,19 +73,21 @@ DG_DEV float denormalize_value(float n, float factor) // normalize.c:38: true IE
 constexpr uint32_t BLOCK = 256;
 constexpr uint32_t WAVES = BLOCK / 64;
 
-constexpr uint32_t ENC_RING = 32;                               // queued words per lane (LDS: 8 KiB per pair)
-constexpr uint32_t ENC_ROWS = 8;                                // rows per fill batch
-constexpr uint32_t ENC_FILL_WORDS = (31 + 65 * ENC_ROWS) / 32;  // most words a batch can add (65-bit worst-case codewords)
-static_assert(ENC_FILL_WORDS < ENC_RING, "ring too small");
+constexpr uint32_t ENC_RING = 32; // queued words per lane (LDS: 8 KiB per group of three waves)
+constexpr uint32_t ENC_ROWS = 8;  // rows per fill batch
 
 // A channel can be coded over several launches, each taking the next range of rows (the host pipeline uploads a batch of
 // few, long channels in bands and codes every band as it lands; a stream longer than one call's 2^25 samples): the state
 // of a lane's three state machines between two launches, ENC_STATE_WORDS dwords per channel, [word][channel]:
-//   0..5   the filler: bit queue (acc low, acc high, cnt), last sample (low, high), its verdict
-//   6..10  the writer: F (low, high), fcnt, the held-back word, pos
-//   11..15 the coder: the interval (A, B), the model (c1, tot, mps)
-//   16, 17 the writer again: err, lost_ones (BacWriter: the all-ones words dropped last beyond a short slab's end)
+enum EncStateWord : uint32_t
+{
+  ES_Q_ACC_LO, ES_Q_ACC_HI, ES_Q_CNT, ES_LAST_LO, ES_LAST_HI, ES_FILL_ERR, // 0..5   the filler: bit queue, last sample (its high half: valuesize 33..64), its verdict
+  ES_F_LO, ES_F_HI, ES_FCNT, ES_PREV, ES_POS,                              // 6..10  the writer: F, fcnt, the held-back word, pos
+  ES_A, ES_B, ES_C1, ES_TOT, ES_MPS,                                       // 11..15 the coder: the interval (A, B), the model (c1, tot, mps)
+  ES_WRITE_ERR, ES_LOST_ONES // 16, 17 the writer again: err, lost_ones (BacWriter: the all-ones words dropped last beyond a short slab's end)
+};
 constexpr uint32_t ENC_STATE_WORDS = 18;
+static_assert(ES_LOST_ONES + 1 == ENC_STATE_WORDS, "one name per word");
 constexpr uint32_t ENC_SEG_CONTINUES = 1; // the launch goes on from saved state
 constexpr uint32_t ENC_SEG_MORE = 2;      // more rows follow in a later launch: no EOF symbol, state saved
 
@@ -106,6 +108,79 @@ struct EncodeArgs
   uint32_t seg_flags;        // ENC_SEG_*
   const uint64_t *count = nullptr; // VAR variants: [C], channel c is rows 0 .. count[c] - 1 of its column (no segments then)
 };
+
+struct EncChannelState // word k of the lane's channel of the state: s[k]
+{
+  uint32_t *word0; // NULL: no state, or a lane without a channel
+  size_t C;
+  DG_DEV uint32_t &operator[](EncStateWord k) const
+  {
+    return word0[k * C];
+  }
+};
+
+// Each machine's registers from the state and back, a pair per machine
+DG_DEV void restore_filler(EncChannelState s, BitQueue &q, uint32_t &last, uint64_t &last64, int32_t &verdict)
+{
+  q.acc = ((uint64_t)s[ES_Q_ACC_HI] << 32) | s[ES_Q_ACC_LO];
+  q.cnt = s[ES_Q_CNT];
+  last = s[ES_LAST_LO];
+  last64 = ((uint64_t)s[ES_LAST_HI] << 32) | last;
+  verdict = (int32_t)s[ES_FILL_ERR];
+}
+template <bool W64>
+DG_DEV void save_filler(EncChannelState s, const BitQueue &q, uint32_t last, uint64_t last64, int32_t verdict)
+{
+  s[ES_Q_ACC_LO] = (uint32_t)q.acc;
+  s[ES_Q_ACC_HI] = (uint32_t)(q.acc >> 32);
+  s[ES_Q_CNT] = q.cnt;
+  s[ES_LAST_LO] = W64 ? (uint32_t)last64 : last;
+  s[ES_LAST_HI] = (uint32_t)(last64 >> 32);
+  s[ES_FILL_ERR] = (uint32_t)verdict;
+}
+
+template <bool ADAPTIVE, uint32_t RAW>
+DG_DEV void restore_coder(EncChannelState s, BacCoder<ADAPTIVE, RAW> &enc)
+{
+  enc.L = ((uint64_t)2 << 32) | s[ES_A];
+  enc.B = s[ES_B];
+  enc.c1 = s[ES_C1];
+  enc.tot = s[ES_TOT];
+  enc.mps = s[ES_MPS];
+}
+template <bool ADAPTIVE, uint32_t RAW>
+DG_DEV void save_coder(EncChannelState s, const BacCoder<ADAPTIVE, RAW> &enc) // after a last dump: the state keeps A only
+{
+  s[ES_A] = (uint32_t)enc.L;
+  s[ES_B] = enc.B;
+  s[ES_C1] = enc.c1;
+  s[ES_TOT] = enc.tot;
+  s[ES_MPS] = enc.mps;
+}
+
+template <uint32_t ORING>
+DG_DEV void restore_writer(EncChannelState s, BacWriter<ORING> &wr)
+{
+  wr.err = (int32_t)s[ES_WRITE_ERR];
+  wr.lost_ones = s[ES_LOST_ONES];
+  wr.F = ((uint64_t)s[ES_F_HI] << 32) | s[ES_F_LO];
+  wr.fcnt = s[ES_FCNT];
+  wr.prev = s[ES_PREV];
+  wr.pos = s[ES_POS];
+  wr.drained = wr.pos > 0u ? wr.pos - 1u : 0u; // everything but the held-back word is in the slab
+}
+template <uint32_t ORING>
+DG_DEV void save_writer(EncChannelState s, BacWriter<ORING> &wr)
+{
+  wr.drain_lane(); // everything but the held-back word to the slab
+  s[ES_F_LO] = (uint32_t)wr.F;
+  s[ES_F_HI] = (uint32_t)(wr.F >> 32);
+  s[ES_FCNT] = wr.fcnt;
+  s[ES_PREV] = wr.prev;
+  s[ES_POS] = wr.pos;
+  s[ES_WRITE_ERR] = (uint32_t)wr.err;
+  s[ES_LOST_ONES] = wr.lost_ones;
+}
 
 // `symbols`: no channel of the batch codes more symbols than this (cum[0] starts at 3 and grows by one per symbol until
 // it halves at MAX_FREQUENCY): short channels need only the beginning of the table
@@ -146,8 +221,8 @@ DG_DEV void load_div_table(uint32_t *tab, const uint32_t *gtab, uint64_t symbols
 // F32IN: the rows are float32 readings; Normalize (normalize.c:16-24) runs on each value as it leaves LDS, in front of
 // the difference -- one launch, no int32 intermediate in HBM.  With W64 the rows stay one dword per lane (floats) and
 // the normalized value is 64 bits wide (valuesize 33..64, normalize.c:21-24 with io_int_t = int64).
-// How the two waves of a pair share their SIMD: how long a wave with nothing to do sleeps (units of 64 cycles) and the
-// issue priority of the coding waves.  Compile-time, so that tools/tunebench.py can time variants side by side.
+// How the three waves of a group share their SIMD: how long a wave with nothing to do sleeps (units of 64 cycles) and the
+// waves' issue priorities (the coder's: dega_lane.hpp).  Compile-time, so that tools/tunebench.py can time variants side by side.
 #ifndef DG_ENC_FILL_SLEEP
 #define DG_ENC_FILL_SLEEP 12
 #endif
@@ -162,14 +237,6 @@ DG_DEV void load_div_table(uint32_t *tab, const uint32_t *gtab, uint64_t symbols
 #endif
 #ifndef DG_ENC_WRITE_PRIO
 #define DG_ENC_WRITE_PRIO 1
-#endif
-#ifndef DG_ENC_CODE_PRIO
-#define DG_ENC_CODE_PRIO 3
-#endif
-// A step of the coding wave with lanes that have no word queued takes the masked steady path for all 64 lanes, the dry
-// ones coding an empty part (1), or the general route under an exec mask (0)
-#ifndef DG_ENC_DRY_LANES
-#define DG_ENC_DRY_LANES 1
 #endif
 #ifndef DG_DEC_PARSE_SLEEP
 #define DG_DEC_PARSE_SLEEP 6
@@ -192,15 +259,15 @@ DG_DEV void load_div_table(uint32_t *tab, const uint32_t *gtab, uint64_t symbols
 #ifndef DG_DEC_TAKES // unconditional short-codeword takes per pass of the parsing wave
 #define DG_DEC_TAKES 4
 #endif
-constexpr uint32_t ENC_PAIRS = 4;                 // groups of three waves per workgroup
-constexpr uint32_t ENC_BLOCK = ENC_PAIRS * 192;   // threads per workgroup: a filling, a coding and a writing wave per 64 channels
-constexpr uint32_t ENC_CHANNELS = ENC_PAIRS * 64; // channels per workgroup
+constexpr uint32_t ENC_GROUPS = 4;                 // groups of three waves per workgroup
+constexpr uint32_t ENC_BLOCK = ENC_GROUPS * 192;   // threads per workgroup: a filling, a coding and a writing wave per 64 channels
+constexpr uint32_t ENC_CHANNELS = ENC_GROUPS * 64; // channels per workgroup
 constexpr uint32_t ENC_PUB_DONE = 1u << 24, ENC_PUB_BAD = 1u << 25;
 
-// ---- the helping wave(s): fill and write -------------------------------------------------------------------------------
-// FILLS / WRITES: which of the two this wave is.  (A wave each: the coding wave of a SIMD must never wait for either, and
-// three waves get more instructions per cycle out of a SIMD than two -- one wave doing both left the coder waiting for
-// room a sixth of its time.)
+// ---- the filling wave ----------------------------------------------------------------------------------------------------
+// (The helpers are a wave each: the coding wave of a SIMD must never wait for either, and three waves get more instructions
+// per cycle out of a SIMD than two -- one wave doing both left the coder waiting for room a sixth of its time.)
+// NARROW: valuesize < 32 -- the samples are masked to valuesize bits and the difference is range checked against it.
 // VAR: a ragged batch (a.count).  A lane's channel ends with its own count; the wave's row loop ends at the largest count of
 // its lanes (T_end) and takes the straight-line batch only while every lane still has ROWS rows (T_all, the smallest
 // count): both are wave uniform, computed once.  Rows at or beyond a lane's count are fetched with the others and may hold
@@ -208,55 +275,33 @@ constexpr uint32_t ENC_PUB_DONE = 1u << 24, ENC_PUB_BAD = 1u << 25;
 // publication per wave, after the wave's last row: a lane that ended early simply has no new word for the coder, which
 // already steps with lanes that have none.  count[c] > T: the channel is coded as empty and the writer reports
 // ERR_INVALID_VALUE and 0 bits.  Without VAR, T_end and T_all are a.T and the code is what it was.
-template <bool NARROW, uint32_t ROWS, uint32_t RING, uint32_t RAW, uint32_t ORING, bool W64, bool F32IN, bool FILLS, bool WRITES, bool VAR = false>
-DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const uint32_t *raw_col, uint32_t *oring_col, uint32_t *rows_wave, uint32_t *pub_mine,
-                                const uint32_t *pub_peer, uint32_t lane, size_t c, bool live, size_t c_wave0)
+template <bool NARROW, uint32_t ROWS, uint32_t RING, bool W64, bool F32IN, bool VAR>
+DG_DEV void encode_filling_wave(const EncodeArgs &a, uint32_t *ring_col, uint32_t *rows_wave, uint32_t *pub_mine, const uint32_t *pub_coder, uint32_t lane, size_t c,
+                                bool live, size_t c_wave0)
 {
-  static_assert(FILLS != WRITES, "a helper fills or writes");
-  // NARROW: valuesize < 32 -- the samples are masked to valuesize bits and the difference is range checked against it
   constexpr uint32_t FILL_WORDS = (31 + (W64 ? 127 : 65) * ROWS) / 32; // most words a batch can add (worst-case codewords)
   constexpr bool ROWS64 = W64 && !F32IN; // rows of two dwords per lane
-  constexpr uint32_t GROUP = ORING / 2;  // staged words stored together: 64 bytes for the narrow batches' 32-word staging ring
   static_assert(FILL_WORDS < RING, "ring too small");
-  static_assert(GROUP % 4 == 0 && GROUP >= 4, "whole 16-byte stores");
   const uint32_t vmask = NARROW ? (1u << (a.valuesize & 31u)) - 1u : 0xFFFFFFFFu, vhalf = NARROW ? 1u << ((a.valuesize - 1u) & 31u) : 0x80000000u;
+
   const bool continues = a.seg_state != nullptr && (a.seg_flags & ENC_SEG_CONTINUES) != 0u;
   const bool more = a.seg_state != nullptr && (a.seg_flags & ENC_SEG_MORE) != 0u;
-  uint32_t *const state = a.seg_state != nullptr && live ? a.seg_state + c : nullptr; // word k at state[k * C]
-
+  const EncChannelState state{a.seg_state != nullptr && live ? a.seg_state + c : nullptr, a.C};
   BitQueue q;
   q.init();
   uint32_t last = 0; // diff.c:11
   uint64_t last64 = 0;
   int32_t lane_err = OK;
-  BacWriter<ORING> wr;
-  wr.init(live ? reinterpret_cast<uint32_t *>(a.out + c * a.cap) : nullptr, live ? (uint32_t)(a.cap / 4) : 0u, oring_col);
   if (continues && live)
-  {
-    q.acc = ((uint64_t)state[1 * a.C] << 32) | state[0];
-    q.cnt = state[2 * a.C];
-    last = state[3 * a.C];
-    last64 = ((uint64_t)state[4 * a.C] << 32) | last;
-    lane_err = (int32_t)state[5 * a.C];
-    wr.err = (int32_t)state[16 * a.C];
-    wr.lost_ones = state[17 * a.C];
-    wr.F = ((uint64_t)state[7 * a.C] << 32) | state[6 * a.C];
-    wr.fcnt = state[8 * a.C];
-    wr.prev = state[9 * a.C];
-    wr.pos = state[10 * a.C];
-    wr.drained = wr.pos > 0u ? wr.pos - 1u : 0u; // everything but the held-back word is in the slab
-  }
-  uint32_t rrd = 0; // raw entries absorbed
+    restore_filler(state, q, last, last64, lane_err);
   uint32_t mine = 0; // VAR: the lane's count
-  bool over = false; // VAR: count[c] > T
   if constexpr (VAR)
   {
     const uint64_t n = live ? a.count[c] : 0u;
-    over = n > a.T;
-    mine = over ? 0u : (uint32_t)n; // (T <= 2^25)
+    mine = n > a.T ? 0u : (uint32_t)n; // (T <= 2^25)
   }
-  const size_t T_end = VAR && FILLS ? (size_t)wave_uniform(wave_max_u32(mine)) : a.T;
-  const size_t T_all = VAR && FILLS ? (size_t)wave_uniform(wave_min_u32(live ? mine : 0xFFFFFFFFu)) : a.T;
+  const size_t T_end = VAR ? (size_t)wave_uniform(wave_max_u32(mine)) : a.T;
+  const size_t T_all = VAR ? (size_t)wave_uniform(wave_min_u32(live ? mine : 0xFFFFFFFFu)) : a.T;
 
   // Input rows travel HBM -> LDS directly (LDS-DMA, `global_load_lds_dword`: one 256-byte row segment per wave
   // instruction, no VGPR destination) and are read from LDS by the next fill; the next batch is requested right after a
@@ -422,17 +467,17 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
     t += left < ROWS ? left : ROWS;
   };
 
-  wave_priority<(WRITES ? DG_ENC_WRITE_PRIO : DG_ENC_FILL_PRIO)>();
-  if (FILLS && T_end > 0)
+  wave_priority<DG_ENC_FILL_PRIO>();
+  if (T_end > 0)
     issue_rows(0);
-  bool tail_placed = !FILLS; // the final, partial word is in the ring (or stays in the state) and "done" is published
+  bool tail_placed = false; // the final, partial word is in the ring (or stays in the state) and "done" is published
   uint32_t pub_flags = 0;
   for (;;)
   {
-    const uint32_t cp = peer_load(pub_peer);
+    const uint32_t cp = peer_load(pub_coder);
     bool worked = false;
-    // ---- fill: the same ROWS rows for every lane, as soon as every lane's ring has room for what they may add -----------
-    if (FILLS && t < T_end)
+    // the same ROWS rows for every lane, as soon as every lane's ring has room for what they may add
+    if (t < T_end)
     {
       const bool room = ((q.wr - cp) & 0xFFFFu) + FILL_WORDS <= RING;
       if (wave_all(room))
@@ -452,7 +497,7 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
     // batch of worst-case codewords can leave the ring full to the last slot (RING words queued), and the next slot is
     // then the oldest word the coder has not taken yet.  When more rows follow in a later launch the bits stay in the
     // queue (saved with the state) and the coder gets no partial word.
-    if (FILLS && t >= T_end && !tail_placed && !wave_any(((q.wr - cp) & 0xFFFFu) >= RING))
+    if (t >= T_end && !tail_placed && !wave_any(((q.wr - cp) & 0xFFFFu) >= RING))
     {
       uint32_t tail_bits = 0;
       if (!more)
@@ -464,9 +509,42 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
       tail_placed = true;
       worked = true;
     }
-    // ---- write: the coder's raw entries, oldest first, all lanes in step ---------------------------------------------------
-    uint32_t avail = WRITES ? ((cp >> 16) - rrd) & 0xFFu : 0u;
-    if (WRITES && wave_any(avail != 0u))
+    peer_store(pub_mine, (q.wr & 0xFFFFu) | pub_flags);
+    if (tail_placed)
+      break; // through: the tail is placed
+    if (!worked)
+      wave_sleep<DG_ENC_FILL_SLEEP>(); // (a poll costs a dozen instructions of a SIMD that has none to spare)
+  }
+  wait_vector_memory(); // no DMA may still be writing to LDS when the workgroup's allocation is released
+  if (live && more)
+    save_filler<W64>(state, q, last, last64, lane_err);
+}
+
+// ---- the writing wave ----------------------------------------------------------------------------------------------------
+template <uint32_t RAW, uint32_t ORING, bool VAR>
+DG_DEV void encode_writing_wave(const EncodeArgs &a, const uint32_t *raw_col, uint32_t *oring_col, uint32_t *pub_mine, const uint32_t *pub_coder, size_t c, bool live)
+{
+  constexpr uint32_t GROUP = ORING / 2; // staged words stored together: 64 bytes for the narrow batches' 32-word staging ring
+  static_assert(GROUP % 4 == 0 && GROUP >= 4, "whole 16-byte stores");
+
+  const bool continues = a.seg_state != nullptr && (a.seg_flags & ENC_SEG_CONTINUES) != 0u;
+  const bool more = a.seg_state != nullptr && (a.seg_flags & ENC_SEG_MORE) != 0u;
+  const EncChannelState state{a.seg_state != nullptr && live ? a.seg_state + c : nullptr, a.C};
+  BacWriter<ORING> wr;
+  wr.init(live ? reinterpret_cast<uint32_t *>(a.out + c * a.cap) : nullptr, live ? (uint32_t)(a.cap / 4) : 0u, oring_col);
+  if (continues && live)
+    restore_writer(state, wr);
+  uint32_t rrd = 0; // raw entries absorbed
+  const bool over = VAR && (live ? a.count[c] : 0u) > a.T; // VAR: count[c] > T, reported below (see the filling wave)
+
+  wave_priority<DG_ENC_WRITE_PRIO>();
+  for (;;)
+  {
+    const uint32_t cp = peer_load(pub_coder);
+    bool worked = false;
+    // the coder's raw entries, oldest first, all lanes in step
+    uint32_t avail = ((cp >> 16) - rrd) & 0xFFu;
+    if (wave_any(avail != 0u))
     {
       uint32_t budget = GROUP; // entries per pass: the staging ring takes a group's worth on top of what waits to be stored
       // The steady state: every lane has the four entries of a fast word step, a word held back, and room in F for all
@@ -551,60 +629,33 @@ DG_DEV void encode_helping_wave(const EncodeArgs &a, uint32_t *ring_col, const u
       }
       worked = true;
     }
-    peer_store(pub_mine, (q.wr & 0xFFFFu) | ((rrd & 0xFFu) << 16) | pub_flags);
-    // through: the tail is placed (filling), the coder has written its last entry and every entry is absorbed (writing)
-    if (tail_placed && (!WRITES || wave_all((cp & ENC_PUB_DONE) != 0u && (((cp >> 16) - rrd) & 0xFFu) == 0u)))
+    peer_store(pub_mine, (rrd & 0xFFu) << 16);
+    // through: the coder has written its last entry and every entry is absorbed
+    if (wave_all((cp & ENC_PUB_DONE) != 0u && (((cp >> 16) - rrd) & 0xFFu) == 0u))
       break;
     if (!worked)
-      wave_sleep<(WRITES ? DG_ENC_WRITE_SLEEP : DG_ENC_FILL_SLEEP)>(); // (a poll costs a dozen instructions of a SIMD that has none to spare)
+      wave_sleep<DG_ENC_WRITE_SLEEP>(); // (a poll costs a dozen instructions of a SIMD that has none to spare)
   }
-  if (FILLS)
-    wait_vector_memory(); // no DMA may still be writing to LDS when the workgroup's allocation is released
   if (!live)
     return;
   if (more)
-  {
-    // the state machines' registers to the state (the coder saves its own); everything but the held-back word to the slab
-    if (FILLS)
-    {
-      state[0] = (uint32_t)q.acc;
-      state[1 * a.C] = (uint32_t)(q.acc >> 32);
-      state[2 * a.C] = q.cnt;
-      state[3 * a.C] = W64 ? (uint32_t)last64 : last;
-      state[4 * a.C] = (uint32_t)(last64 >> 32);
-      state[5 * a.C] = (uint32_t)lane_err;
-    }
-    if (WRITES)
-    {
-      wr.drain_lane();
-      state[6 * a.C] = (uint32_t)wr.F;
-      state[7 * a.C] = (uint32_t)(wr.F >> 32);
-      state[8 * a.C] = wr.fcnt;
-      state[9 * a.C] = wr.prev;
-      state[10 * a.C] = wr.pos;
-      state[16 * a.C] = (uint32_t)wr.err;
-      state[17 * a.C] = wr.lost_ones;
-    }
-  }
+    save_writer(state, wr); // (the filler and the coder save their own)
   else
   {
     // the last launch of a channel: the writer reports its length and the verdict -- a value out of range (the filler's
-    // finding: diff.c:17-18, normalize.c:21; a filler in a wave of its own publishes it with "done" and the coder hands
-    // it on with its own) before a slab too small
-    if (WRITES)
-    {
+    // finding: diff.c:17-18, normalize.c:21; the filler publishes it with "done" and the coder hands it on with its own)
+    // before a slab too small
 #if defined(DEGA_DIAG) && (DEGA_DIAG & 32) && !defined(DEGA_SIM)
-      (void)wr.finish();
+    (void)wr.finish();
 #else
-      a.out_bits[c] = wr.finish();
+    a.out_bits[c] = wr.finish();
 #endif
-      const bool bad_value = FILLS ? lane_err != OK : (peer_load(pub_peer) & ENC_PUB_BAD) != 0u;
-      a.err[c] = bad_value ? ERR_INVALID_VALUE : wr.err;
-      if (VAR && over)
-      {
-        a.out_bits[c] = 0;
-        a.err[c] = ERR_INVALID_VALUE;
-      }
+    const bool bad_value = (peer_load(pub_coder) & ENC_PUB_BAD) != 0u;
+    a.err[c] = bad_value ? ERR_INVALID_VALUE : wr.err;
+    if (VAR && over)
+    {
+      a.out_bits[c] = 0;
+      a.err[c] = ERR_INVALID_VALUE;
     }
   }
 }
@@ -621,15 +672,9 @@ DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const u
   enc.init(raw_col, pub_writer);
   const bool continues = a.seg_state != nullptr && (a.seg_flags & ENC_SEG_CONTINUES) != 0u;
   const bool more = a.seg_state != nullptr && (a.seg_flags & ENC_SEG_MORE) != 0u;
-  uint32_t *const state = a.seg_state != nullptr && live ? a.seg_state + c : nullptr;
+  const EncChannelState state{a.seg_state != nullptr && live ? a.seg_state + c : nullptr, a.C};
   if (continues && live)
-  {
-    enc.L = ((uint64_t)2 << 32) | state[11 * a.C];
-    enc.B = state[12 * a.C];
-    enc.c1 = state[13 * a.C];
-    enc.tot = state[14 * a.C];
-    enc.mps = state[15 * a.C];
-  }
+    restore_coder(state, enc);
   uint32_t rd = 0; // ring words coded so far
   // The helper's word as read one step ago: a ring word may only be read after a count that covers it, and waiting for
   // the count before asking for the word would put two LDS round trips at the head of every step.  One step late costs
@@ -693,69 +738,40 @@ DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const u
     }
     // The same with some lanes at a halving of the counts or a change of the division shift (CLS_SPLIT: the word in two
     // parts, see BacCoder): the masked fast path for all 64 lanes -- whole words for the others
-#if DG_ENC_DRY_LANES
     // ... and with dry lanes: the filler works in row lockstep and the lanes' bit rates differ, so a lane below the wave's
     // highest rate has no word queued now and then (a lane past its last word never has, nor has a lane without a
     // channel).  Such a lane codes the empty part -- no symbol, no count, its four entries hold no bits -- and the wave
     // keeps to straight-line code.  Every lane needs room for the four entries and a fast class, the dry ones too: theirs
     // keeps the fetch of the division magics inside the table.
+    if (wave_all(room4 && enc.cls <= CLS_SPLIT) && wave_any(has))
     {
-      if (wave_all(room4 && enc.cls <= CLS_SPLIT) && wave_any(has))
+      if (waiting)
       {
-        if (waiting)
-        {
-          wave_priority<DG_ENC_CODE_PRIO>();
-          waiting = false;
-        }
-#if defined(DG_COUNTING)
-        const bool dry_step = wave_any(!has);
-#endif
-        enc.template encode_word<false, 8, true>(word, tab, Mg, !has);
-        const bool whole = has && (enc.cls != CLS_SPLIT || enc.after_part(word));
-        rd += whole ? 1u : 0u;
-        enc.safe -= has && enc.safe != 0u ? 1u : 0u;
-        const bool again = whole && enc.safe == 0u;
-        if (wave_any(again))
-        {
-          if (again)
-            enc.classify();
-        }
-        peer_store(pub_mine, (rd & 0xFFFFu) | ((enc.rwr & 0xFFu) << 16));
-#if defined(DG_COUNTING)
-        if (dry_step)
-          DG_COUNT(4);
-        else
-          DG_COUNT(1);
-#endif
-        continue;
+        wave_priority<DG_ENC_CODE_PRIO>();
+        waiting = false;
       }
-    }
-#else
-    if constexpr (ADAPTIVE)
-    {
-      if (wave_all(ready && enc.cls <= CLS_SPLIT))
+#if defined(DG_COUNTING)
+      const bool dry_step = wave_any(!has);
+#endif
+      enc.template encode_word<false, 8, true>(word, tab, Mg, !has);
+      const bool whole = has && (enc.cls != CLS_SPLIT || enc.after_part(word));
+      rd += whole ? 1u : 0u;
+      enc.safe -= has && enc.safe != 0u ? 1u : 0u;
+      const bool again = whole && enc.safe == 0u;
+      if (wave_any(again))
       {
-        if (waiting)
-        {
-          wave_priority<DG_ENC_CODE_PRIO>();
-          waiting = false;
-        }
-        enc.template encode_word<false, 8, true>(word, tab, Mg);
-        const bool whole = enc.cls != CLS_SPLIT || enc.after_part(word);
-        rd += whole ? 1u : 0u;
-        enc.safe -= enc.safe != 0u ? 1u : 0u;
-        const bool again = whole && enc.safe == 0u;
-        if (wave_any(again))
-        {
-          if (again)
-            enc.classify();
-        }
-        peer_store(pub_mine, (rd & 0xFFFFu) | ((enc.rwr & 0xFFu) << 16));
+        if (again)
+          enc.classify();
+      }
+      peer_store(pub_mine, (rd & 0xFFFFu) | ((enc.rwr & 0xFFu) << 16));
+#if defined(DG_COUNTING)
+      if (dry_step)
+        DG_COUNT(4);
+      else
         DG_COUNT(1);
-        continue;
-      }
-    }
 #endif
+      continue;
+    }
     // (the slower word paths write eight entries; the bit path waits for room by itself).  A lane with a word but no room
     // for its entries holds the whole wave up: the writer never waits for this wave, so room comes, and the lanes stay in
     // step -- a wave whose lanes take turns needs more steps, each with its exec masks and merges
@@ -864,11 +880,7 @@ DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const u
     if (more)
     {
       enc.dump_when_room();
-      state[11 * a.C] = (uint32_t)enc.L;
-      state[12 * a.C] = enc.B;
-      state[13 * a.C] = enc.c1;
-      state[14 * a.C] = enc.tot;
-      state[15 * a.C] = enc.mps;
+      save_coder(state, enc);
     }
     else
       enc.finish(tab);
@@ -891,7 +903,7 @@ DG_DEV void encode_coding_wave(const EncodeArgs &a, const uint32_t *tab, const u
 constexpr uint32_t ENC_SHORT_TABLE = 8192;
 constexpr size_t ENC_SHORT_T = (ENC_SHORT_TABLE - 70) / 65; // 124
 template <bool ADAPTIVE, bool NARROW = false, uint32_t ROWS = ENC_ROWS, uint32_t RING = ENC_RING, uint32_t RAW = ENC_RAW, uint32_t ORING = ENC_ORING, bool W64 = false,
-          bool F32IN = false, uint32_t GROUPS = ENC_PAIRS, uint32_t TABW = DIV_TABLE_SIZE, bool VAR = false>
+          bool F32IN = false, uint32_t GROUPS = ENC_GROUPS, uint32_t TABW = DIV_TABLE_SIZE, bool VAR = false>
 __global__ void __launch_bounds__(GROUPS * 192) dega_encode_kernel(const EncodeArgs a)
 {
   constexpr uint32_t LDS_ROWS = (W64 && !F32IN) ? 2 * ROWS : ROWS;
@@ -936,9 +948,9 @@ __global__ void __launch_bounds__(GROUPS * 192) dega_encode_kernel(const EncodeA
   if (role == 1)
     encode_coding_wave<ADAPTIVE, RING, RAW>(a, tab, ring_col, raw_col, pub_coder, pub_filler, pub_writer, lane, c, live);
   else if (role == 0)
-    encode_helping_wave<NARROW, ROWS, RING, RAW, ORING, W64, F32IN, true, false, VAR>(a, ring_col, raw_col, oring_col, rows_wave, pub_filler, pub_coder, lane, c, live, c_wave0);
+    encode_filling_wave<NARROW, ROWS, RING, W64, F32IN, VAR>(a, ring_col, rows_wave, pub_filler, pub_coder, lane, c, live, c_wave0);
   else
-    encode_helping_wave<NARROW, ROWS, RING, RAW, ORING, W64, F32IN, false, true, VAR>(a, ring_col, raw_col, oring_col, rows_wave, pub_writer, pub_coder, lane, c, live, c_wave0);
+    encode_writing_wave<RAW, ORING, VAR>(a, raw_col, oring_col, pub_writer, pub_coder, c, live);
 }
 
 // =====================================================================================================================
@@ -2013,7 +2025,7 @@ inline bool launch(const EncodeVariant &v, const EncodeArgs &a, L &&launch_one)
         if constexpr (!(NARROW && W64) && !(VAR && !F32) && !(SHORT && (!AD || W64 || VAR)))
         {
           constexpr EncodeRings R = SHORT ? ENC_RINGS_SHORT : (W64 ? ENC_RINGS_W64 : ENC_RINGS_STANDARD);
-          launch_one(dega_encode_kernel<AD, NARROW, R.rows, R.ring, R.raw, R.oring, W64, F32, ENC_PAIRS, SHORT ? ENC_SHORT_TABLE : DIV_TABLE_SIZE, VAR>, grid,
+          launch_one(dega_encode_kernel<AD, NARROW, R.rows, R.ring, R.raw, R.oring, W64, F32, ENC_GROUPS, SHORT ? ENC_SHORT_TABLE : DIV_TABLE_SIZE, VAR>, grid,
                      ENC_BLOCK, a);
         }
       },

@@ -719,26 +719,10 @@ DG_DEV SegWord diff_seg(uint32_t u, uint32_t &last, uint32_t half = 0x80000000u)
   return r;
 }
 
-// diff + seg for the common case, branch free: returns w (the codeword's value; its length is 2*floor(log2 w) + 1 bits).
-// w = zigzag(-v) + 1 with v = x - last:  v > 0 -> 2v,  v <= 0 -> 2|v| + 1  (seg.c:25-28 + the "+1" of seg.c:13).
-// Only valid when the result fits 16 bits (codeword <= 31 bits); `wide` says when it does not (or v = INT32_MIN).
-template <bool NARROW = false>
-DG_DEV uint32_t diff_seg_short(uint32_t u, uint32_t &last, bool &ok, bool &wide, uint32_t half = 0x80000000u)
-{
-  const uint32_t nv = last - u;                                    // -v, low 32 bits
-  if (NARROW)
-    ok = half - nv < 2u * half;                                    // -half <= v <= half - 1
-  else
-    ok = (u >= last) == ((int32_t)nv <= 0);                        // diff.c:17-18: the true difference fits int32
-  last = u;
-  const uint32_t w = ((nv << 1) ^ (uint32_t)((int32_t)nv >> 31)) + 1u;
-  wide = (w >> 16) != 0u || nv == 0x80000000u;
-  return w;
-}
-
 // The steady state of a 32-bit channel, as few instructions as it takes: w for samples whose difference is known to fit
 // (both below 2^31 -- the caller ORs the samples of a batch and looks at the top bit once) -- and is short (the caller ORs
-// the w of a batch and looks above bit 15 once; v = INT32_MIN cannot occur between samples below 2^31).
+// the w of a batch and looks above bit 15 once; v = INT32_MIN cannot occur between samples below 2^31).  Branch free:
+// w = zigzag(-v) + 1 with v = x - last:  v > 0 -> 2v,  v <= 0 -> 2|v| + 1  (seg.c:25-28 + the "+1" of seg.c:13).
 DG_DEV uint32_t diff_seg_steady(uint32_t u, uint32_t &last)
 {
   const uint32_t nv = last - u; // -v, low 32 bits

@@ -1,7 +1,7 @@
 """Inputs whose channels code at very different bit rates, shared by tests/test_kernel_sim_dry_lanes.py (emulator) and
 tests/test_gpu_dry_lanes.py (GPU).  The encoder's filling wave works in row lockstep, so within a wave every lane below the
 highest rate has no word queued in many of the coding wave's steps ("dry lanes"); such steps take the masked steady word
-path with the dry lanes coding an empty part (dega_kernels.hpp, DG_ENC_DRY_LANES).  Every channel of every case is held
+path with the dry lanes coding an empty part (dega_kernels.hpp, encode_coding_wave).  Every channel of every case is held
 to oracle.orc.encode_i32 byte for byte: stream, bit count and status, which is 0 for all of them."""
 import numpy as np
 

@@ -103,13 +103,15 @@ extern "C" __attribute__((visibility("default"))) int sim_synth(int32_t *x, size
 }
 
 
-// the channels' rows coded over several launches (rows [cuts[k], cuts[k+1]) each), the lanes' state saved in between
-extern "C" __attribute__((visibility("default"))) int sim_encode_segments(const int32_t *x, size_t C, size_t T, size_t ld, int adaptive, const size_t *cuts, int ncuts, uint8_t *out,
-                                                                       size_t cap, uint64_t *bits, int32_t *err)
+// the channels' rows coded over several launches (rows [cuts[k], cuts[k+1]) each), the lanes' state saved in between; x, f32,
+// factor and valuesize as run_encode takes them
+extern "C" __attribute__((visibility("default"))) int sim_encode_segments(const void *x, size_t C, size_t T, size_t ld, int f32, float factor, int adaptive, int valuesize,
+                                                                       const size_t *cuts, int ncuts, uint8_t *out, size_t cap, uint64_t *bits, int32_t *err)
 {
   std::vector<uint32_t> state(ENC_STATE_WORDS * C, 0xDEADBEEFu);
+  const size_t row_bytes = ld * (valuesize > 32 && f32 == 0 ? sizeof(int64_t) : sizeof(int32_t));
   for (int k = 0; k + 1 < ncuts; k++)
-    if (run_encode(x + cuts[k] * ld, C, cuts[k + 1] - cuts[k], ld, false, 0.0f, adaptive, 32, out, cap, bits, err, state.data(),
+    if (run_encode(static_cast<const uint8_t *>(x) + cuts[k] * row_bytes, C, cuts[k + 1] - cuts[k], ld, f32 != 0, factor, adaptive, valuesize, out, cap, bits, err, state.data(),
                    (k > 0 ? ENC_SEG_CONTINUES : 0u) | (k + 2 < ncuts ? ENC_SEG_MORE : 0u)) != 0)
       return -1;
   (void)T;

@@ -63,7 +63,7 @@ int main(int argc, char **argv)
     std::unique_ptr<uint8_t[]> out(new uint8_t[C * cap]);
     memset(out.get(), 0, C * cap);
     if (call == 1)
-      sim_encode_segments(x.get(), C, T, C, adaptive, cuts.get(), (int)ncuts, out.get(), cap, bits.get(), err.get());
+      sim_encode_segments(x.get(), C, T, C, 0, 0.0f, adaptive, 32, cuts.get(), (int)ncuts, out.get(), cap, bits.get(), err.get());
     else
       sim_encode(x.get(), C, T, C, adaptive, out.get(), cap, bits.get(), err.get());
     ok = write_block(g, C, cap, err.get(), bits.get(), out.get());

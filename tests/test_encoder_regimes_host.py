@@ -34,7 +34,7 @@ def sim():
     subprocess.run(["make", "-s", "-C", SIM_DIR], check=True)
     S = C.CDLL(os.path.join(SIM_DIR, "libdega_sim.so"))
     S.sim_encode.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    S.sim_encode_segments.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    S.sim_encode_segments.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     return S
 
 
@@ -47,7 +47,7 @@ def emulated(S, x, ad, cap, cuts=None):
         S.sim_encode(x.ctypes.data, Cn, Tn, Cn, ad, out.ctypes.data, cap, bits.ctypes.data, err.ctypes.data)
     else:
         cu = np.array(cuts, dtype=np.uint64)
-        S.sim_encode_segments(x.ctypes.data, Cn, Tn, Cn, ad, cu.ctypes.data, len(cu), out.ctypes.data, cap, bits.ctypes.data, err.ctypes.data)
+        S.sim_encode_segments(x.ctypes.data, Cn, Tn, Cn, 0, 0.0, ad, 32, cu.ctypes.data, len(cu), out.ctypes.data, cap, bits.ctypes.data, err.ctypes.data)
     return out, bits, err
 
 

@@ -216,6 +216,22 @@ def test_rows_uploaded_in_bands_beside_the_running_kernel(dca, ctx, monkeypatch)
     assert (ef == 0).all() and (bf == bg).all() and pf.tobytes() == pg.tobytes()
 
 
+def test_bands_carry_a_64_bit_last_sample_between_launches(dca, ctx, monkeypatch):
+    """The same bands where the state between two launches holds a 64-bit `last` (ES_LAST_LO, ES_LAST_HI): int64 samples at
+    value size 40 and the float entry at value size 48 -- the streams are those of one launch."""
+    T, Cn = 6000, 130
+    rng = np.random.default_rng(40)
+    x = ((1 << 37) + np.cumsum(rng.integers(-(1 << 20), (1 << 20) + 1, (T, Cn)), axis=0)).astype(np.int64)
+    v = (np.cumsum(rng.normal(0, 4e8, (T, Cn)), axis=0) + 3e11).astype(np.float32)  # * 100: around 2^45
+    for arr, kw in ((x, dict(valuesize=40, samples=dca.SAMPLES_I64)), (v, dict(valuesize=48, samples=dca.SAMPLES_F32, factor=100.0))):
+        monkeypatch.setenv("DEGA_PIPELINE_BAND_BYTES", "65536")
+        pb, ob, bb, eb = ctx.encode_job(arr, adaptive=1, **kw)
+        monkeypatch.setenv("DEGA_PIPELINE_BAND_BYTES", "0")
+        p0, o0, b0, e0 = ctx.encode_job(arr, adaptive=1, **kw)
+        assert (eb == 0).all() and (e0 == 0).all(), kw
+        assert (bb == b0).all() and pb.tobytes() == p0.tobytes(), kw
+
+
 def test_pinned_samples_read_in_place_by_the_kernel(dca, ctx, monkeypatch):
     """A chunk that is all columns of the caller's pinned array is not uploaded: the encode kernel's filling waves fetch
     the rows from host memory themselves.  Same streams as through the copy engine (DEGA_PIPELINE_IN_PLACE=0) and as

@@ -174,7 +174,7 @@ def test_channels_coded_over_several_launches_with_saved_state(sim):
     """The rows of a batch coded in ranges, one launch per range, every lane's state (bit queue, interval, model, finished
     bits, held-back word) saved in between (EncodeArgs::seg_state): the streams must be those of one launch -- cuts inside a
     seg-bit word, right after the first row, ranges of a single row, an empty last range, channels in error."""
-    sim.sim_encode_segments.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    sim.sim_encode_segments.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     rng = np.random.default_rng(5)
     T, Cn = 700, 130  # a ragged last wave
     x = (np.cumsum(rng.integers(-300, 301, (T, Cn)), axis=0) + 70000).astype(np.int32)
@@ -188,7 +188,7 @@ def test_channels_coded_over_several_launches_with_saved_state(sim):
             bits = np.zeros(Cn, dtype=np.uint64)
             err = np.zeros(Cn, dtype=np.int32)
             cu = np.array(cuts, dtype=np.uint64)
-            sim.sim_encode_segments(x.ctypes.data, Cn, T, Cn, ad, cu.ctypes.data, len(cuts), out.ctypes.data, cap, bits.ctypes.data, err.ctypes.data)
+            sim.sim_encode_segments(x.ctypes.data, Cn, T, Cn, 0, 0.0, ad, 32, cu.ctypes.data, len(cuts), out.ctypes.data, cap, bits.ctypes.data, err.ctypes.data)
             assert (err == want_err).all(), (ad, cuts)
             ok = want_err == 0
             assert (bits[ok] == want_bits[ok]).all(), (ad, cuts)

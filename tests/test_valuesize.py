@@ -533,6 +533,54 @@ def test_kernel_logic_float_entries_without_counts(sim, vs, ad):
     check_float_back(want, back, derr, (vs, ad))
 
 
+SEGMENT_C, SEGMENT_T = 70, 300  # one full wave and a wave of six lanes
+SEGMENT_CUTS = [0, 1, 2, 3, 150, 151, 300, 300]  # single rows, no multiples of the 64-bit variants' four rows per batch, an empty last range
+
+
+def _segment_input(kind, vs):
+    """(samples, float flag, factor): int64 walks that start near 2^37, so that the high half of `last` is never 0, or this
+    file's float walks; in either, one channel that leaves the range in the middle (the filler's verdict crosses launches)"""
+    if kind == "f32":
+        v, lim = float_walks(vs, SEGMENT_C, SEGMENT_T)
+        v[160:, 3] = lim * 1.5  # normalize.c:21
+        return v, 1, FLOAT_FACTOR
+    rng = np.random.default_rng(vs)
+    x = (1 << 37) + np.cumsum(rng.integers(-(1 << 20), (1 << 20) + 1, (SEGMENT_T, SEGMENT_C)), axis=0)
+    x[160:, 5] = (1 << vs) - 1  # a difference of more than 2^(valuesize - 1): diff.c:17-18
+    return np.ascontiguousarray(x.astype(np.int64)), 0, 0.0
+
+
+@pytest.mark.parametrize("ad", (1, 0))
+@pytest.mark.parametrize("kind,vs", (("i64", 40), ("f32", 32), ("f32", 48)))
+def test_kernel_logic_segments_carry_a_64_bit_last_sample_and_the_float_entry(sim, kind, vs, ad):
+    """Channels coded over several launches with saved state (EncodeArgs::seg_state) where the filler's words 3 and 4 hold a
+    64-bit `last` -- int64 containers, the float entry above 32 bits -- and through the float entry at 32 bits: status, bit
+    count and stream are those of one launch, which the tests above hold to the oracle."""
+    Z, P, I = C.c_size_t, C.c_void_p, C.c_int
+    sim.sim_encode_segments.argtypes = [P, Z, Z, Z, I, C.c_float, I, I, P, I, P, Z, P, P]
+    sim.sim_encode_f32.argtypes = [P, Z, Z, Z, C.c_float, I, I, P, Z, P, P]
+    _sim64(sim)
+    x, f32, factor = _segment_input(kind, vs)
+    Cn, T, cap = SEGMENT_C, SEGMENT_T, float_cap(SEGMENT_T, vs)
+    want_out, got_out = np.zeros((Cn, cap), dtype=np.uint8), np.zeros((Cn, cap), dtype=np.uint8)
+    want_bits, got_bits = np.zeros(Cn, dtype=np.uint64), np.zeros(Cn, dtype=np.uint64)
+    want_err, got_err = np.full(Cn, 99, dtype=np.int32), np.full(Cn, 99, dtype=np.int32)
+    if f32:
+        assert sim.sim_encode_f32(x.ctypes.data, Cn, T, Cn, factor, ad, vs, want_out.ctypes.data, cap, want_bits.ctypes.data, want_err.ctypes.data) == 0
+    else:
+        assert sim.sim_encode64(x.ctypes.data, Cn, T, Cn, ad, vs, want_out.ctypes.data, cap, want_bits.ctypes.data, want_err.ctypes.data) == 0
+    assert int((want_err == orc.ERROR_INVALID_VALUE).sum()) == 1 and int((want_err == 0).sum()) == Cn - 1
+    cu = np.array(SEGMENT_CUTS, dtype=np.uint64)
+    assert sim.sim_encode_segments(x.ctypes.data, Cn, T, Cn, f32, factor, ad, vs, cu.ctypes.data, len(cu), got_out.ctypes.data, cap, got_bits.ctypes.data,
+                                   got_err.ctypes.data) == 0
+    assert (got_err == want_err).all(), (kind, vs, ad)
+    ok = want_err == 0
+    assert (got_bits[ok] == want_bits[ok]).all(), (kind, vs, ad)
+    for c in np.nonzero(ok)[0]:
+        nb = (int(want_bits[c]) + 7) // 8
+        assert got_out[c, :nb].tobytes() == want_out[c, :nb].tobytes(), (kind, vs, ad, int(c))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("vs", (17, 40))
 def test_gpu_float_entries_static_model_at_other_value_sizes(vs):
