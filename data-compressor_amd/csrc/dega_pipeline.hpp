@@ -1248,6 +1248,9 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &job, const uint8_t *pack
   };
   std::vector<DecChunk> chunks(plan.nchunks);
   const bool samples_pinned = is_pinned(samples), packed_pinned = is_pinned(packed);
+  const bool all_uploads_first = (size_t)plan.nslots >= plan.nchunks && decode_uploads_first();
+  TRACE("decode share: C %zu T %zu, %zu chunks of %zu channels, %d slots, %s", j.C, j.T, plan.nchunks, plan.chunk_channels, plan.nslots,
+        all_uploads_first ? "all uploads first" : "chunk by chunk");
 
   // (the slot's stream is idle when stage1a runs -- it synchronises it -- so nothing of the slot's is still in use)
   const bool one_upload_stream = packed_pinned && decode_uploads_first();
@@ -1302,6 +1305,7 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &job, const uint8_t *pack
       memset(reports, 0, sizeof(uint32_t) * waves);
       if (sl.s2 == nullptr)
         HIP_TRY(ctx, hipStreamCreateWithFlags(&sl.s2, hipStreamNonBlocking), DEGA_ERROR_LIBRARY_CALL);
+      TRACE("decode chunk %zu: %zu bands of %zu rows, sent home beside the kernel", k, (j.T + ch.band_rows - 1) / ch.band_rows, ch.band_rows);
     }
     if ((r = launch_decode(ctx, (const uint8_t *)sl.b.p, cap, dm.bits, cj, j.C, sl.c.p, out_count != nullptr ? dm.counts : nullptr, dm.err, sl.s, reports,
                            (uint32_t)ch.band_rows)) != DEGA_OK)
@@ -1359,7 +1363,7 @@ static int decode_share(dega_hip_ctx *ctx, const Shape &job, const uint8_t *pack
         out_count[ch.c0 + i] = hm.counts[i];
     return DEGA_OK;
   };
-  if ((size_t)plan.nslots >= plan.nchunks && decode_uploads_first())
+  if (all_uploads_first)
   {
     // Every chunk has a slot of its own: all the uploads are enqueued before the first decode kernel.  HIP puts the
     // streams on a few hardware queues that take their packets in order; with upload and kernel enqueued chunk by chunk,

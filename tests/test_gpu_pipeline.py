@@ -184,10 +184,12 @@ def test_order_of_the_enqueues_does_not_change_the_result(dca, ctx, monkeypatch)
 
 
 def test_rows_uploaded_in_bands_beside_the_running_kernel(dca, ctx, monkeypatch):
-    """Few, long channels: the encode kernel starts before the samples are there and takes the rows as the bands of the
-    upload arrive (EncodeArgs::rows_ready); the decode kernel's rows go home in bands while it is still running
-    (DecodeArgs::rows_done).  Forced onto small batches with small bands -- many band ends, a ragged last wave, pageable and
-    pinned memory, a float batch -- and compared with the device-resident kernel's streams / the input."""
+    """Few, long channels: the rows go up in bands on a second stream and every band is coded by a launch of its own behind
+    the band's event, each launch taking the lanes' state where the one before left it (the slot's seg_state,
+    EncodeArgs::seg_state); the decode kernel's rows go home in bands while it is still running (DecodeArgs::rows_done).
+    Forced onto small batches with small bands -- many band ends, a ragged last wave, pageable and pinned memory, a float
+    batch -- and compared with the device-resident kernel's streams / the input.  One chunk only: bands in several chunks
+    are in test_gpu_pipeline_bands_chunks.py."""
     import torch
     monkeypatch.setenv("DEGA_PIPELINE_BAND_BYTES", "65536")
     for Cn, T in ((300, 5000), (64, 9001), (1030, 700)):
