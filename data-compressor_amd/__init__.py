@@ -108,6 +108,11 @@ _SIGNATURES = {
     "dega_hip_encode_levels_f32_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _P, _Z, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "dega_hip_csv_write_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_uint, _Z, C.c_int, _P, _Z, _P, _P, _P]),
     "dega_hip_lzmh_encode_levels_f32_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _P, _Z, C.c_uint, _Z, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dega_hip_encode_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_int, C.c_int, C.c_int, _P, _Z, _P, _P, _P]),
+    "dega_hip_encode64_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_int, C.c_int, _P, _Z, _P, _P, _P]),
+    "dega_hip_encode_segment_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _Z, _Z, C.c_int, C.c_int, _P, _Z, _P, _P, _P, C.c_uint, _P]),
+    "dega_hip_encode_var_job_host": (C.c_int, [_P, _P, _P, _P, _P, _Z, _P, _P, _P]),
+    "dega_hip_group_encode_var": (C.c_int, [_P, _P, _P, _P, _P, _Z, _P, _P, _P]),
     "dega_hip_to_time_major_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _Z, _P, _P, _Z, _P]),
     "dega_hip_to_channel_major_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _Z, _P, _P, _Z, _P]),
     "dega_hip_profile": (C.c_int, [_P, C.c_int]),
@@ -239,7 +244,7 @@ class _JobCalls:
     (every device).  Subclasses provide _enc_fn / _dec_fn / _handle / _check."""
 
     def encode_job(self, x_tc, adaptive=1, valuesize=32, samples=SAMPLES_I32, factor=100.0, packed_cap=None, channels=None, packed=None, num_values=1,
-                   layout="time", T=None):
+                   layout="time", T=None, count=None):
         """x_tc: [T, ld] array of the sample type (channels = the first `channels` columns, default all).
         Returns (packed uint8 [total], offsets uint64 [C+1], bits uint64 [C], err int32 [C]).
         num_values != 1 (float32 samples only): every num_values consecutive readings of a channel are summed on the
@@ -247,9 +252,22 @@ class _JobCalls:
         layout="channel": the array is [C, ld] instead, one series per row (DEGA_SAMPLES_CHANNEL_MAJOR), T = the first T
         values of every row (default all); it goes up as it lies and is transposed on the device.  The array must then
         be C-contiguous and of the sample type (big-endian samples: dtype ">i4"); the results are those of the
-        time-major call on its transpose."""
+        time-major call on its transpose.
+        count (numpy uint64 array, one entry per channel: what decode_job(var=True) returns): a ragged batch -- channel c is
+        coded from its first count[c] values and what lies behind them influences nothing (dega_hip_encode_var_job_host /
+        dega_hip_group_encode_var).  Any sample type, both layouts; num_values must be 1.  The array is taken as it is,
+        as for layout="channel": C-contiguous and of the sample type."""
         import numpy as np
         assert layout in ("time", "channel"), 'layout is "time" or "channel"'
+        if count is not None:
+            assert int(num_values) == 1, "a counted job codes the samples as they are: num_values must be 1"
+            Cn, Tn, _, _ = dims = _host_layout(x_tc, layout, samples, channels, T)
+            assert isinstance(count, np.ndarray) and count.dtype == np.uint64 and count.ndim == 1 and count.flags.c_contiguous, \
+                "count must be a contiguous numpy uint64 array"
+            assert count.size == Cn, "count has one entry per channel"
+            assert packed is None or (isinstance(packed, np.ndarray) and packed.dtype == np.uint8 and packed.flags.c_contiguous and packed.ndim == 1)
+            return self._encode_packed(self._enc_var_fn(), (count.ctypes.data,), "encode_job(count=, layout=%s)" % layout, x_tc, Tn, adaptive, valuesize,
+                                       samples, factor, packed_cap, channels, packed, dims)
         if layout == "channel":
             Cn, Tn, _, _ = dims = _host_layout(x_tc, layout, samples, channels, T)
             num_values = int(num_values)
@@ -419,6 +437,9 @@ class Group(_JobCalls):
     def _dec_fn(self):
         return library().dega_hip_group_decode
 
+    def _enc_var_fn(self):
+        return library().dega_hip_group_encode_var
+
     def _enc_agg_fn(self):
         return library().dega_hip_group_encode_agg
 
@@ -474,6 +495,9 @@ class Context(_JobCalls):
     def _dec_fn(self):
         return library().dega_hip_decode_job_host
 
+    def _enc_var_fn(self):
+        return library().dega_hip_encode_var_job_host
+
     def _enc_agg_fn(self):
         return library().dega_hip_encode_agg_job_host
 
@@ -512,12 +536,28 @@ class Context(_JobCalls):
         return _P(torch.cuda.current_stream().cuda_stream)
 
     # ---- device-resident API (torch tensors) ---------------------------------------------------------------------
-    def encode(self, x_tc, adaptive=1, cap=None, out=None, bits=None, err=None, valuesize=32):
-        """x_tc: int32 CUDA tensor [T, ld>=C].  Returns (out uint8 [C, cap], bits int64 [C] (bit lengths), err int32 [C])."""
+    def encode(self, x_tc, adaptive=1, cap=None, out=None, bits=None, err=None, valuesize=32, count=None, channels=None, samples=SAMPLES_I32):
+        """x_tc: int32 CUDA tensor [T, ld>=C].  Returns (out uint8 [C, cap], bits int64 [C] (bit lengths), err int32 [C]).
+        count (int64 CUDA tensor, one per channel): a ragged batch -- channel c is coded from its first count[c] rows
+        (dega_hip_encode_var_dev), valuesize 1..32; channels: the first `channels` columns of the rows (default all);
+        samples: SAMPLES_I32, or SAMPLES_BE32 for byte-swapped words.  Returns (out, bits, err, counts) as encode_f32 does."""
         import torch
         T, ld = x_tc.shape
         Cn = ld
         assert x_tc.dtype == torch.int32 and x_tc.is_cuda and x_tc.is_contiguous()
+        if count is not None:
+            Cn = ld if channels is None else int(channels)
+            assert 0 <= Cn <= ld, "channels must be at most the row pitch"
+            if cap is None:
+                cap = worst_case_bytes(T)
+            out = torch.zeros((Cn, cap), dtype=torch.uint8, device=x_tc.device)
+            bits = torch.zeros(Cn, dtype=torch.int64, device=x_tc.device)
+            err = torch.zeros(Cn, dtype=torch.int32, device=x_tc.device)
+            ret = library().dega_hip_encode_var_dev(self._h, x_tc.data_ptr(), Cn, T, ld, _count_ptr(count, Cn, x_tc.device), int(adaptive), int(valuesize),
+                                                    int(samples), out.data_ptr(), cap, bits.data_ptr(), err.data_ptr(), self._stream())
+            self._check(ret, "dega_hip_encode_var_dev")
+            return out, bits, err, count
+        assert channels is None and samples == SAMPLES_I32, "channels= and samples= go with count="
         if cap is None:
             cap = worst_case_bytes(T)
         if out is None:
@@ -531,12 +571,15 @@ class Context(_JobCalls):
         self._check(ret, "dega_hip_encode_dev")
         return out, bits, err
 
-    def encode_segments(self, x_tc, cuts, adaptive=1, cap=None, valuesize=32):
+    def encode_segments(self, x_tc, cuts, adaptive=1, cap=None, valuesize=32, count=None):
         """The rows of x_tc ([T, C] int32 CUDA tensor) coded in ranges [cuts[k], cuts[k+1]), one launch each, the lanes' state
-        kept in device memory in between (dega_hip_encode_segment_dev).  Returns (out, bits, err) of the whole channels."""
+        kept in device memory in between (dega_hip_encode_segment_dev).  Returns (out, bits, err) of the whole channels.
+        count (int64 CUDA tensor, one per channel): a ragged batch, every launch with row0 = cuts[k] and T_total = T
+        (dega_hip_encode_segment_var_dev); the streams are those of encode(count=)."""
         import torch
         T, Cn = x_tc.shape
         assert x_tc.dtype == torch.int32 and x_tc.is_cuda and x_tc.is_contiguous() and cuts[0] == 0 and cuts[-1] == T
+        count_ptr = None if count is None else _count_ptr(count, Cn, x_tc.device)
         if cap is None:
             cap = worst_case_bytes(T)
         out = torch.zeros((Cn, cap), dtype=torch.uint8, device=x_tc.device)
@@ -547,6 +590,12 @@ class Context(_JobCalls):
             flags = (1 if k > 0 else 0) | (2 if k + 2 < len(cuts) else 0)
             rows = x_tc[cuts[k]:cuts[k + 1]]
             ptr = rows.data_ptr() if cuts[k + 1] > cuts[k] else x_tc.data_ptr()
+            if count is not None:
+                ret = library().dega_hip_encode_segment_var_dev(self._h, ptr, Cn, cuts[k + 1] - cuts[k], Cn, count_ptr, cuts[k], T, int(adaptive),
+                                                                int(valuesize), out.data_ptr(), cap, bits.data_ptr(), err.data_ptr(), state.data_ptr(),
+                                                                flags, self._stream())
+                self._check(ret, "dega_hip_encode_segment_var_dev")
+                continue
             ret = library().dega_hip_encode_segment_dev(self._h, ptr, Cn, cuts[k + 1] - cuts[k], Cn, int(adaptive), int(valuesize), out.data_ptr(), cap,
                                                         bits.data_ptr(), err.data_ptr(), state.data_ptr(), flags, self._stream())
             self._check(ret, "dega_hip_encode_segment_dev")

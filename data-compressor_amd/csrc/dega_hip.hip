@@ -298,6 +298,7 @@ struct Shape
   int adaptive, valuesize, samples;
   float factor;
   bool cmajor = false; // host jobs only: the caller's array is [C][ld], ld >= T (DEGA_SAMPLES_CHANNEL_MAJOR; `samples` holds the type alone)
+  const uint64_t *count = nullptr; // host encode jobs only: a HOST array of C counts, one per channel (the launches get device copies as arguments of their own)
 };
 
 static int check_job_shape(dega_hip_ctx *ctx, const Shape &j, size_t cap)
@@ -315,19 +316,23 @@ static int check_job_shape(dega_hip_ctx *ctx, const Shape &j, size_t cap)
 }
 
 static int launch_encode(dega_hip_ctx *ctx, const void *x, const Shape &j, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err,
-                         hipStream_t s, uint32_t *seg_state = nullptr, uint32_t seg_flags = 0, const uint64_t *count = nullptr)
+                         hipStream_t s, uint32_t *seg_state = nullptr, uint32_t seg_flags = 0, const uint64_t *count = nullptr, size_t row0 = 0,
+                         size_t T_total = 0)
 {
   int ret;
   if ((ret = check_job_shape(ctx, j, cap)) != DEGA_OK)
     return ret;
-  if (count != nullptr && (j.samples != DEGA_SAMPLES_F32 || seg_state != nullptr || ((uintptr_t)count & 7u) != 0))
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode: counts go with float32 samples only, never with a segment state, and are 8-byte aligned", hipSuccess);
+  if (count != nullptr && ((uintptr_t)count & 7u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode: count must be a device array of C 64-bit entries, 8-byte aligned", hipSuccess);
+  // counts with a segment state: the launch is rows row0 .. row0 + T - 1 of a series of T_total rows
+  if (count != nullptr && seg_state != nullptr && (T_total > DEGA_MAX_T || row0 > T_total || j.T > T_total - row0))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode segment: row0 + T_seg <= T_total <= 2^25", hipSuccess);
   if (j.C == 0)
     return DEGA_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
   const bool f32 = j.samples == DEGA_SAMPLES_F32;
   const EncodeArgs a = encode_args(x, j.C, j.T, j.ld, out, cap, out_bits, err, ctx->div_magic, j.valuesize, j.samples == DEGA_SAMPLES_BE32, j.factor, seg_state,
-                                   seg_flags, count);
+                                   seg_flags, count, row0, T_total);
   {
     LaunchTimer lt(ctx, 0, s);
     if (!launch(encode_variant(j.C, j.T, seg_state != nullptr, count != nullptr, j.valuesize, f32, j.adaptive != 0), a, OnStream{s}))
@@ -398,6 +403,39 @@ extern "C" int dega_hip_encode_segment_dev(dega_hip_ctx *ctx, const int32_t *x_t
   static_assert(DEGA_SEGMENT_CONTINUES == ENC_SEG_CONTINUES && DEGA_SEGMENT_MORE == ENC_SEG_MORE, "the flags of the header are the kernel's");
   return launch_encode(ctx, x_tc, shape_of(C, T_seg, ld, adaptive, valuesize, DEGA_SAMPLES_I32), out, cap, out_bits, err, (hipStream_t)stream,
                        (uint32_t *)state, flags);
+}
+
+// what the counted integer entry points add to their uniform twins' refusals (check_counts, below, with its `err`)
+static int check_counts(dega_hip_ctx *ctx, size_t C, size_t T, const uint64_t *count, uint64_t *const *out_count, size_t K, const int32_t *err);
+
+extern "C" int dega_hip_encode_var_dev(dega_hip_ctx *ctx, const int32_t *x_tc, size_t C, size_t T, size_t ld, const uint64_t *count, int adaptive,
+                                       int valuesize, int samples, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream)
+{
+  int ret;
+  if ((ret = check_shape(ctx, C, T, ld, cap, valuesize)) != DEGA_OK)
+    return ret;
+  if (samples != DEGA_SAMPLES_I32 && samples != DEGA_SAMPLES_BE32)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode: samples must be DEGA_SAMPLES_I32 or DEGA_SAMPLES_BE32", hipSuccess);
+  if ((ret = check_counts(ctx, C, T, count, nullptr, 0, err)) != DEGA_OK)
+    return ret;
+  return launch_encode(ctx, x_tc, shape_of(C, T, ld, adaptive, valuesize, samples), out, cap, out_bits, err, (hipStream_t)stream, nullptr, 0, count);
+}
+
+extern "C" int dega_hip_encode_segment_var_dev(dega_hip_ctx *ctx, const int32_t *x_tc, size_t C, size_t T_seg, size_t ld, const uint64_t *count, size_t row0,
+                                               size_t T_total, int adaptive, int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err,
+                                               void *state, unsigned flags, void *stream)
+{
+  int ret;
+  if ((ret = check_shape(ctx, C, T_seg, ld, cap, valuesize)) != DEGA_OK)
+    return ret;
+  if (state == nullptr || (flags & ~(unsigned)(DEGA_SEGMENT_CONTINUES | DEGA_SEGMENT_MORE)) != 0u || ((uintptr_t)state & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode segment: state (device memory, dega_hip_encode_state_bytes) and flags DEGA_SEGMENT_*", hipSuccess);
+  if (T_total > DEGA_MAX_T || row0 > T_total || T_seg > T_total - row0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode segment: row0 + T_seg <= T_total <= 2^25", hipSuccess);
+  if ((ret = check_counts(ctx, C, T_total, count, nullptr, 0, err)) != DEGA_OK)
+    return ret;
+  return launch_encode(ctx, x_tc, shape_of(C, T_seg, ld, adaptive, valuesize, DEGA_SAMPLES_I32), out, cap, out_bits, err, (hipStream_t)stream,
+                       (uint32_t *)state, flags, count, row0, T_total);
 }
 
 extern "C" int dega_hip_decode_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld,
@@ -1112,6 +1150,15 @@ extern "C" int dega_hip_encode64_dev(dega_hip_ctx *ctx, const int64_t *x_tc, siz
   if ((ret = check_shape64(ctx, C, T, ld, cap, valuesize)) != DEGA_OK)
     return ret;
   return launch_encode(ctx, x_tc, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_I64), out, cap, out_bits, err, (hipStream_t)stream);
+}
+
+extern "C" int dega_hip_encode64_var_dev(dega_hip_ctx *ctx, const int64_t *x_tc, size_t C, size_t T, size_t ld, const uint64_t *count, int adaptive,
+                                         int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream)
+{
+  int ret;
+  if ((ret = check_shape64(ctx, C, T, ld, cap, valuesize)) != DEGA_OK || (ret = check_counts(ctx, C, T, count, nullptr, 0, err)) != DEGA_OK)
+    return ret;
+  return launch_encode(ctx, x_tc, shape_of(C, T, ld, adaptive, valuesize, DEGA_SAMPLES_I64), out, cap, out_bits, err, (hipStream_t)stream, nullptr, 0, count);
 }
 
 extern "C" int dega_hip_decode64_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t T, size_t ld,

@@ -106,7 +106,10 @@ struct EncodeArgs
   float factor, lo, hi;      // normalization factor; range of normalize.c:21 for the value size, rounded to float by the host compiler
   uint32_t *seg_state;       // NULL: whole channels in one launch.  Else [ENC_STATE_WORDS][C], see above
   uint32_t seg_flags;        // ENC_SEG_*
-  const uint64_t *count = nullptr; // VAR variants: [C], channel c is rows 0 .. count[c] - 1 of its column (no segments then)
+  const uint64_t *count = nullptr; // VAR variants: [C], channel c is rows 0 .. count[c] - 1 of its column
+  // VAR variants with a segment state: the rows of the channels that earlier launches took, and the length of the whole
+  // series (the same in every launch of it).  A launch of whole channels: 0 and T.
+  size_t row0 = 0, T_total = 0;
 };
 
 struct EncChannelState // word k of the lane's channel of the state: s[k]
@@ -275,6 +278,14 @@ constexpr uint32_t ENC_PUB_DONE = 1u << 24, ENC_PUB_BAD = 1u << 25;
 // publication per wave, after the wave's last row: a lane that ended early simply has no new word for the coder, which
 // already steps with lanes that have none.  count[c] > T: the channel is coded as empty and the writer reports
 // ERR_INVALID_VALUE and 0 bits.  Without VAR, T_end and T_all are a.T and the code is what it was.
+// VAR over several launches (a.seg_state): this launch holds rows row0 .. row0 + T - 1 of a series of T_total rows, and
+// the lane's own rows are those of them below its count, clamp(count[c] - row0, 0, T).  "count above T" is judged against
+// T_total and so is the same verdict in every launch.  A lane whose series ended in an earlier launch adds nothing here
+// and saves the state it restored; the coder and the writer carry on as for any lane without new words.
+// Integer rows (the NARROW, big-endian and W64 paths): the steady straight-line batch commits `last` for the whole batch
+// and is taken only while t + ROWS <= T_all, so every row it codes lies below every live lane's count; behind that the
+// per-row writer is guarded by left_mine, in the W64 path too.  The row fetch clamps to the launch's last row (t_last),
+// never to a lane's count: rows beyond a count but inside the image are read and dropped.
 template <bool NARROW, uint32_t ROWS, uint32_t RING, bool W64, bool F32IN, bool VAR>
 DG_DEV void encode_filling_wave(const EncodeArgs &a, uint32_t *ring_col, uint32_t *rows_wave, uint32_t *pub_mine, const uint32_t *pub_coder, uint32_t lane, size_t c,
                                 bool live, size_t c_wave0)
@@ -298,7 +309,8 @@ DG_DEV void encode_filling_wave(const EncodeArgs &a, uint32_t *ring_col, uint32_
   if constexpr (VAR)
   {
     const uint64_t n = live ? a.count[c] : 0u;
-    mine = n > a.T ? 0u : (uint32_t)n; // (T <= 2^25)
+    const uint64_t ahead = n > a.row0 ? n - a.row0 : 0u; // rows of the series from this launch's first on
+    mine = n > a.T_total ? 0u : (uint32_t)(ahead < a.T ? ahead : a.T); // (T <= 2^25)
   }
   const size_t T_end = VAR ? (size_t)wave_uniform(wave_max_u32(mine)) : a.T;
   const size_t T_all = VAR ? (size_t)wave_uniform(wave_min_u32(live ? mine : 0xFFFFFFFFu)) : a.T;
@@ -535,7 +547,7 @@ DG_DEV void encode_writing_wave(const EncodeArgs &a, const uint32_t *raw_col, ui
   if (continues && live)
     restore_writer(state, wr);
   uint32_t rrd = 0; // raw entries absorbed
-  const bool over = VAR && (live ? a.count[c] : 0u) > a.T; // VAR: count[c] > T, reported below (see the filling wave)
+  const bool over = VAR && (live ? a.count[c] : 0u) > a.T_total; // VAR: count[c] > T, reported below (see the filling wave)
 
   wave_priority<DG_ENC_WRITE_PRIO>();
   for (;;)
@@ -1960,7 +1972,7 @@ struct EncodeVariant
   bool narrow;      // valuesize < 32: the samples are masked and range checked against the value size
   bool w64;         // valuesize 33..64: int64 containers
   bool f32;         // float32 input, Normalize fused into the fill phase
-  bool counted;     // a ragged batch: a count per channel (float32 input only)
+  bool counted;     // a ragged batch: a count per channel (any sample type; not with the short table)
   bool short_table; // short channels, and enough of them to fill the chip twice: half the table, small rings, two workgroups per CU
 };
 
@@ -1979,7 +1991,7 @@ inline EncodeVariant encode_variant(size_t C, size_t T, bool segmented, bool cou
 
 inline EncodeArgs encode_args(const void *x, size_t C, size_t T, size_t ld, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, const uint32_t *div_magic,
                               int valuesize, bool big_endian = false, float factor = 0.0f, uint32_t *seg_state = nullptr, uint32_t seg_flags = 0,
-                              const uint64_t *count = nullptr)
+                              const uint64_t *count = nullptr, size_t row0 = 0, size_t T_total = 0)
 {
   EncodeArgs a;
   a.x = reinterpret_cast<const int32_t *>(x);
@@ -2000,6 +2012,8 @@ inline EncodeArgs encode_args(const void *x, size_t C, size_t T, size_t ld, uint
   a.seg_state = seg_state;
   a.seg_flags = seg_flags;
   a.count = count;
+  a.row0 = seg_state != nullptr ? row0 : 0; // (whole channels in one launch: the series is the launch's rows)
+  a.T_total = seg_state != nullptr && count != nullptr ? T_total : T;
   return a;
 }
 
@@ -2015,14 +2029,14 @@ constexpr EncodeRings ENC_RINGS_SHORT{4, 16, 8, 16};
 template <typename L>
 inline bool launch(const EncodeVariant &v, const EncodeArgs &a, L &&launch_one)
 {
-  if ((v.narrow && v.w64) || (v.counted && !v.f32) || (v.short_table && (!v.adaptive || v.w64 || v.counted)))
+  if ((v.narrow && v.w64) || (v.short_table && (!v.adaptive || v.w64 || v.counted)))
     return false; // no such instantiation
   const LaunchGrid grid{(uint32_t)((a.C + ENC_CHANNELS - 1) / ENC_CHANNELS), 1};
   with_bools(
       [&](auto ad, auto narrow, auto w64, auto f32, auto counted, auto short_table) {
         constexpr bool AD = decltype(ad)::value, NARROW = decltype(narrow)::value, W64 = decltype(w64)::value, F32 = decltype(f32)::value,
                        VAR = decltype(counted)::value, SHORT = decltype(short_table)::value;
-        if constexpr (!(NARROW && W64) && !(VAR && !F32) && !(SHORT && (!AD || W64 || VAR)))
+        if constexpr (!(NARROW && W64) && !(SHORT && (!AD || W64 || VAR)))
         {
           constexpr EncodeRings R = SHORT ? ENC_RINGS_SHORT : (W64 ? ENC_RINGS_W64 : ENC_RINGS_STANDARD);
           launch_one(dega_encode_kernel<AD, NARROW, R.rows, R.ring, R.raw, R.oring, W64, F32, ENC_GROUPS, SHORT ? ENC_SHORT_TABLE : DIV_TABLE_SIZE, VAR>, grid,

@@ -716,6 +716,7 @@ struct EncChunk : Chunk
   bool gathered = false, redone = false;
   bool bands = false; // its rows went up in bands, each coded by a launch of its own
   const uint8_t *rows = nullptr; // where the kernels read the chunk's samples: the slot's buffer, or the caller's pinned array in place
+  const uint64_t *counts = nullptr; // a counted job: the chunk's counts on the device (the slot's metadata buffer)
   size_t rows_ld = 0;            // ... and its row pitch in samples
   std::vector<uint8_t> redo_bytes; // a chunk that needed worst-case slabs: its packed streams, already on the host
 };
@@ -743,7 +744,8 @@ static int encode_redo_chunk(dega_hip_ctx *ctx, Pipeline *pl, Slot &sl, const Sh
     sj.C = n; // columns j0 .. j0+n of the chunk's [T][chunk] image; ld stays the image's pitch
     sj.ld = ch.rows_ld;
     int ret;
-    if ((ret = launch_encode(ctx, ch.rows + j0 * sample_bytes(cj), sj, (uint8_t *)pl->redo_slabs.p, wc, dm.bits, dm.err, sl.s)) != DEGA_OK)
+    if ((ret = launch_encode(ctx, ch.rows + j0 * sample_bytes(cj), sj, (uint8_t *)pl->redo_slabs.p, wc, dm.bits, dm.err, sl.s, nullptr, 0,
+                             ch.counts != nullptr ? ch.counts + j0 : nullptr)) != DEGA_OK)
       return ret;
     if ((ret = sizes_home(ctx, sl.s, dm, n, pl->redo_hmeta.p)) != DEGA_OK)
       return ret;
@@ -814,9 +816,15 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
   // is on the slot's stream), and dega_transpose_kernel makes the time-major image in the samples' buffer from there.  No
   // staging buffer of its own: the slabs hold max(cap, T * esz) bytes per channel then, and plan_chunks is told so.
   // Whole chunks only: no bands and no in-place read of pinned memory (the kernel's filling waves read rows).
+  // A counted job (job.count, host): a chunk's counts go up on the slot's stream ahead of its launches, into the `counts`
+  // array of the slot's metadata (free in an encode call), and every launch of the chunk -- whole, in place, per band,
+  // redone -- is the counted one.  The transpose of channel-major samples takes them too: the tails of the time-major
+  // image are zero bits, whatever lies behind a count in the caller's array.
   const bool cmajor = job.cmajor;
+  const uint64_t *const count = job.count;
   Shape j = job;
   j.cmajor = false; // (the chunks' shapes below describe time-major images on the device)
+  j.count = nullptr;
   int ret;
   Pipeline *pl;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
@@ -849,6 +857,14 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
     HIP_TRY(ctx, sl.meta.need(MetaView::bytes(ch.n)), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.hmeta.need(MetaView::bytes(ch.n)), DEGA_ERROR_MEMORY);
     MetaView dm(sl.meta.p, ch.n);
+    if (count != nullptr)
+    {
+      // through the pinned mirror, which is free too (a slot is reused only after its previous chunk's second stage)
+      MetaView hm(sl.hmeta.p, ch.n);
+      memcpy(hm.counts, count + ch.c0, ch.n * sizeof(uint64_t));
+      HIP_TRY(ctx, hipMemcpyAsync(dm.counts, hm.counts, ch.n * sizeof(uint64_t), hipMemcpyHostToDevice, sl.s), DEGA_ERROR_LIBRARY_CALL);
+      ch.counts = dm.counts;
+    }
     Shape cj = chunk_shape(j, ch.n);
     const uint8_t *const src = (const uint8_t *)samples + ch.c0 * (cmajor ? j.ld : 1) * esz;
     const size_t band_rows = cmajor ? 0 : band_rows_of(plan, j, ch.n * esz);
@@ -870,22 +886,22 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
       ch.rows = (const uint8_t *)dev_src;
       ch.rows_ld = j.ld;
       cj.ld = j.ld;
-      if ((r = launch_encode(ctx, ch.rows, cj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
+      if ((r = launch_encode(ctx, ch.rows, cj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s, nullptr, 0, ch.counts)) != DEGA_OK)
         return r;
       TRACE("chunk %zu: read in place", k);
     }
     else if (cmajor)
     {
       HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.b.p, src, j.ld * esz, j.T * esz, ch.n, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
-      if ((r = launch_transpose(ctx, sl.b.p, ch.n, j.T, j.T, esz, nullptr, true, sl.a.p, ch.n, sl.s)) != DEGA_OK ||
-          (r = launch_encode(ctx, sl.a.p, cj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
+      if ((r = launch_transpose(ctx, sl.b.p, ch.n, j.T, j.T, esz, ch.counts, true, sl.a.p, ch.n, sl.s)) != DEGA_OK ||
+          (r = launch_encode(ctx, sl.a.p, cj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s, nullptr, 0, ch.counts)) != DEGA_OK)
         return r;
       TRACE("chunk %zu: channel-major, transposed on the device", k);
     }
     else if (band_rows == 0)
     {
       HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.a.p, src, j.ld * esz, ch.n * esz, j.T, samples_pinned), DEGA_ERROR_LIBRARY_CALL);
-      if ((r = launch_encode(ctx, sl.a.p, cj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
+      if ((r = launch_encode(ctx, sl.a.p, cj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s, nullptr, 0, ch.counts)) != DEGA_OK)
         return r;
     }
     else
@@ -920,7 +936,7 @@ static int encode_share(dega_hip_ctx *ctx, const Shape &job, const void *samples
         Shape bj = cj;
         bj.T = t1 - t0;
         const uint32_t flags = (b > 0 ? ENC_SEG_CONTINUES : 0u) | (b + 1 < nbands ? ENC_SEG_MORE : 0u);
-        if ((r = launch_encode(ctx, dev_rows, bj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s, (uint32_t *)sl.seg_state.p, flags)) != DEGA_OK)
+        if ((r = launch_encode(ctx, dev_rows, bj, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s, (uint32_t *)sl.seg_state.p, flags, ch.counts, t0, j.T)) != DEGA_OK)
           return r;
       }
       TRACE("chunk %zu: %zu bands of %zu rows, one launch each", k, nbands, band_rows);
@@ -1661,6 +1677,8 @@ static int encode_on_group(dega_hip_group *grp, const Shape &j, const void *samp
         ss[g].offsets = rel[g].data();
         ss[g].bits = sink.bits + r0 + cut[g];
         ss[g].err = sink.err + r0 + cut[g];
+        if (j.count != nullptr)
+          sj.count = j.count + r0 + cut[g];
         rets[g] = encode_share(grp->ctx[g], sj, (const uint8_t *)samples + (r0 + cut[g]) * (j.cmajor ? j.ld : 1) * esz, ss[g], false, runs[g]);
       });
     for (std::thread &t : th)
@@ -1765,6 +1783,38 @@ extern "C" int dega_hip_encode_job_host(dega_hip_ctx *ctx, const dega_hip_job *j
   if (job == nullptr || offsets == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
   return encode_on_ctx(ctx, shape_from_job(job), samples, packed_sink(packed, packed_cap, offsets, out_bits, err));
+}
+
+// ---- the counted job: a count per channel, host memory -------------------------------------------------------------------
+
+static Shape counted_shape(const dega_hip_job *job, const uint64_t *count)
+{
+  Shape j = shape_from_job(job);
+  j.count = count;
+  return j;
+}
+
+extern "C" int dega_hip_encode_var_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const uint64_t *count, const void *samples, uint8_t *packed,
+                                            size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err)
+{
+  if (ctx == nullptr || job == nullptr || offsets == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (count == nullptr && job->C != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "encode: count must be a host array of job->C entries", hipSuccess);
+  return encode_on_ctx(ctx, counted_shape(job, count), samples, packed_sink(packed, packed_cap, offsets, out_bits, err));
+}
+
+extern "C" int dega_hip_group_encode_var(dega_hip_group *grp, const dega_hip_job *job, const uint64_t *count, const void *samples, uint8_t *packed,
+                                         size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err)
+{
+  if (grp == nullptr || job == nullptr || offsets == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (count == nullptr && job->C != 0)
+  {
+    snprintf(grp->last_error, sizeof(grp->last_error), "encode: count must be a host array of job->C entries");
+    return DEGA_ERROR_INVALID_VALUE;
+  }
+  return encode_on_group(grp, counted_shape(job, count), samples, packed_sink(packed, packed_cap, offsets, out_bits, err));
 }
 
 // ---- K granularities from one upload ---------------------------------------------------------------------------------------

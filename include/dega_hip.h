@@ -413,7 +413,7 @@ int dega_hip_lzmh_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t ca
    output counts / lengths / bits of 0; its neighbours are unaffected.  Host-side refusals, alignment rules, the scratch
    buffers with their event protocol and the stream semantics are the uniform twin's; in addition a null or misaligned
    count / out_count[k] and T >= 2^32 are refused, and C != 0 with T = 0 still launches (the counts decide).  A count
-   never goes together with a segment state (there is no counted dega_hip_encode_segment_dev).
+   goes together with a segment state through dega_hip_encode_segment_var_dev alone (integer samples, below).
    Cost: a wave walks rows up to the largest count among its 64 channels.  The aggregate's loop is the uniform kernel's
    while every lane of the wave still has rows and selects per lane behind that; the coder's filling wave takes its
    straight-line batch only while every lane still has a full batch of rows, and the general per-row writer from the
@@ -429,6 +429,26 @@ int dega_hip_aggregate_levels_var_dev(dega_hip_ctx *ctx, const float *v_tc, size
 /* dega_hip_encode_f32_dev over a ragged batch: valuesize 1 .. 64; cap and the limit of 2^25 samples are judged against T. */
 int dega_hip_encode_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, float factor, int adaptive,
                                 int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream);
+/* dega_hip_encode_dev / dega_hip_encode64_dev over a ragged batch: one meter per channel, each stream ending where its
+   input ends, which is the reference's ordinary case (one file per meter: diff.c:12-21 reads until the input is out,
+   seg.c:34-41 and bac.c:152-162 end the stream there).  Channel c's status, bit length and bytes are those of the uniform
+   twin on that channel alone with T = count[c]; rows at or beyond count[c] reach neither the stream, nor the range checks
+   of diff.c:17-18, nor the last value.  They are the inverse of dega_hip_decode_var_dev / dega_hip_decode64_var_dev.
+   samples: DEGA_SAMPLES_I32 or DEGA_SAMPLES_BE32 (byte-swapped words); valuesize 1 .. 32 (encode64: int64 samples,
+   33 .. 64).  Refusals are the uniform twin's (T > 2^25 among them) and those of the counts above. */
+int dega_hip_encode_var_dev(dega_hip_ctx *ctx, const int32_t *x_tc, size_t C, size_t T, size_t ld, const uint64_t *count, int adaptive, int valuesize,
+                            int samples, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream);
+int dega_hip_encode64_var_dev(dega_hip_ctx *ctx, const int64_t *x_tc, size_t C, size_t T, size_t ld, const uint64_t *count, int adaptive, int valuesize,
+                              uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream);
+/* dega_hip_encode_segment_dev over a ragged batch: this launch holds rows row0 .. row0 + T_seg - 1 of series of T_total
+   rows, x_tc points at row row0.  count and T_total are the same in every call of a series; a channel's own rows in a
+   launch are those below its count, clamp(count[c] - row0, 0, T_seg), a channel that ended in an earlier launch adds
+   nothing, and the end of every stream still comes from the last launch (the one without DEGA_SEGMENT_MORE).  count[c] >
+   T_total is the verdict of every launch.  The streams are those of dega_hip_encode_var_dev over all T_total rows.
+   Refused beside the twin's refusals and the counts': row0 + T_seg > T_total, T_total > 2^25. */
+int dega_hip_encode_segment_var_dev(dega_hip_ctx *ctx, const int32_t *x_tc, size_t C, size_t T_seg, size_t ld, const uint64_t *count, size_t row0,
+                                    size_t T_total, int adaptive, int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *state,
+                                    unsigned flags, void *stream);
 /* dega_hip_encode_levels_f32_dev over a ragged batch: dega_hip_aggregate_levels_var_dev into the aggregate scratch, then the
    counted encoder per level with that level's counts.  out_count[k] is required: it is the intermediate, and what the
    caller needs to decode level k (dega_hip_decode_f32_dev with out_count).  A level with num_values 1 is coded from v_tc
@@ -475,6 +495,18 @@ int dega_hip_encode_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const v
                              uint64_t *offsets, uint64_t *out_bits, int32_t *err);
 int dega_hip_decode_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits,
                              void *samples, uint64_t *out_count, int32_t *err);
+/* dega_hip_encode_job_host over a ragged batch -- series of different lengths in host memory, the reference's one file per
+   meter (diff.c:12-21, seg.c:34-41, bac.c:152-162: every stream ends where its input ends).  count: HOST array of job->C
+   uint64; channel c is the first count[c] samples of its column (of its row, with DEGA_SAMPLES_CHANNEL_MAJOR), and what
+   lies behind them in `samples` is uploaded with the rest but influences nothing.  All four sample types, both layouts,
+   and every path of the uniform job: chunks of channels (each with its share of the counts), pinned rows read in place,
+   bands of rows, the worst-case pass over a chunk whose stream outgrew its slab.  Channel c's bits, err and bytes are
+   those of the uniform job on that channel alone with T = count[c]; count[c] > job->T gives it DEGA_ERROR_INVALID_VALUE,
+   0 bits and no bytes.  It takes what dega_hip_decode_job_host reports in out_count.  A null count with C != 0 is
+   refused.  Not offered: counts with num_values != 1 or levels, series packed back to back with starts[C + 1], skipping
+   the upload of rows that no count reaches, sorting channels by length. */
+int dega_hip_encode_var_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const uint64_t *count, const void *samples, uint8_t *packed,
+                                 size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err);
 /* dega_hip_encode_job_host with the aggregation of aggregate.c in front: job->samples must be DEGA_SAMPLES_F32 (anything
    else, and num_values = 0, give DEGA_ERROR_INVALID_VALUE with nothing written), job->T is the fine-grained length.
    num_values = 1 is dega_hip_encode_job_host itself.  Any larger num_values is dega_hip_encode_levels_job_host (below)
@@ -514,6 +546,9 @@ int dega_hip_group_encode(dega_hip_group *group, const dega_hip_job *job, const 
                           uint64_t *offsets, uint64_t *out_bits, int32_t *err);
 int dega_hip_group_decode(dega_hip_group *group, const dega_hip_job *job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits,
                           void *samples, uint64_t *out_count, int32_t *err);
+/* as dega_hip_encode_var_job_host: the counts are split with the channels */
+int dega_hip_group_encode_var(dega_hip_group *group, const dega_hip_job *job, const uint64_t *count, const void *samples, uint8_t *packed,
+                              size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err);
 int dega_hip_group_encode_agg(dega_hip_group *group, const dega_hip_job *job, size_t num_values, const void *samples, uint8_t *packed,
                               size_t packed_cap, uint64_t *offsets, uint64_t *out_bits, int32_t *err);
 /* as dega_hip_encode_agg_job_host: num_values = 1 is dega_hip_group_encode, any larger one dega_hip_group_encode_levels

@@ -8,7 +8,11 @@ Three distributions of the counts: all equal to T; uniform in [0.9 T, T]; one ch
 wave), the others at T.  Per distribution:
   (a) dega_hip_aggregate_levels_var_dev against dega_hip_aggregate_levels_dev at the level set,
   (b) dega_hip_encode_f32_var_dev against dega_hip_encode_f32_dev (adaptive, valuesize 32),
-  (c) dega_hip_csv_write_var_dev against dega_hip_csv_write_dev (two decimals).
+  (c) dega_hip_csv_write_var_dev against dega_hip_csv_write_dev (two decimals),
+  (d) dega_hip_encode_var_dev against dega_hip_encode_dev on the same readings normalized to int32 (adaptive, valuesize 32),
+  (e) the counted host job against the uniform one (encode_job with and without count=) on --job-channels x --job-samples of
+      those int32 samples in pageable host memory: wall clock around the whole call, the two alternating.
+--parts picks among float (a, b), csv (c), int (d), job (e); default: all of them.
 The uniform twin always runs over all T rows -- it has no other way to take the batch -- so for the ragged distributions it
 does MORE work than the counted call; the like-for-like comparison is the first distribution.
 hipEvents on the stream the launches use (torch.cuda.Event is one), warm-up runs, then the two candidates alternating run
@@ -35,6 +39,9 @@ def main():
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--bytes-per-value", type=int, default=9, help="text stride = samples x this (meter readings need about 8)")
+    ap.add_argument("--parts", nargs="+", default=["float", "csv", "int", "job"], choices=["float", "csv", "int", "job"])
+    ap.add_argument("--job-channels", type=int, default=8192)
+    ap.add_argument("--job-samples", type=int, default=10800)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ragged_bench.txt"))
     args = ap.parse_args()
     import numpy as np
@@ -92,11 +99,76 @@ def main():
             % (what, u["median_ms"], u["fastest_ms"], u["p90_ms"], u["slowest_ms"], w["median_ms"], w["fastest_ms"], w["p90_ms"], w["slowest_ms"],
                w["median_ms"] / u["median_ms"], extra))
 
+    def int_parts(name, count, res):
+        """(d) and (e): integer samples, on the device and through the host job"""
+        import time
+        cd = torch.from_numpy(count).cuda()
+        equal = bool((count == T).all())
+        if "int" in args.parts:
+            x, nerr = ctx.normalize(v, 100.0, 32)
+            torch.cuda.synchronize()
+            assert int((nerr != 0).sum().item()) == 0
+            i_uni = (torch.zeros((Cn, cap), dtype=torch.uint8, device="cuda"), torch.zeros(Cn, dtype=torch.int64, device="cuda"), torch.zeros(Cn, dtype=torch.int32, device="cuda"))
+            i_var = (torch.zeros((Cn, cap), dtype=torch.uint8, device="cuda"), torch.zeros(Cn, dtype=torch.int64, device="cuda"), torch.zeros(Cn, dtype=torch.int32, device="cuda"))
+
+            def int_uni():
+                assert L.dega_hip_encode_dev(ctx._h, x.data_ptr(), Cn, T, Cn, 1, 32, i_uni[0].data_ptr(), cap, i_uni[1].data_ptr(), i_uni[2].data_ptr(), s) == 0
+
+            def int_var():
+                assert L.dega_hip_encode_var_dev(ctx._h, x.data_ptr(), Cn, T, Cn, cd.data_ptr(), 1, 32, dca.SAMPLES_I32, i_var[0].data_ptr(), cap, i_var[1].data_ptr(),
+                                                 i_var[2].data_ptr(), s) == 0
+            int_uni()
+            int_var()
+            torch.cuda.synchronize()
+            assert int((i_var[2] != 0).sum().item()) == 0 and int((i_uni[2] != 0).sum().item()) == 0
+            if equal:
+                assert torch.equal(i_uni[1], i_var[1])
+            for c in sample:
+                n = int(count[c])
+                o, b, e = ctx.encode(x[:n, c : c + 1].contiguous(), 1)
+                torch.cuda.synchronize()
+                nb = (int(b[0].item()) + 7) // 8
+                assert int(b[0].item()) == int(i_var[1][c].item()) and torch.equal(o[0, :nb], i_var[0][c, :nb]), c
+            u, w = alternate(int_uni, int_var)
+            report("encode int32 (32, adaptive)", u, w, "; counted: %.1f Gsamples/s of the samples below the counts" % (float(count.sum()) / (w["median_ms"] * 1e-3) / 1e9))
+            res["encode_i32"] = {"uniform": u, "counted": w}
+            del i_uni, i_var, x
+        if "job" in args.parts:
+            jc, jt = min(args.job_channels, Cn), min(args.job_samples, T)
+            xh = ctx.normalize(v[:jt, :jc].contiguous(), 100.0, 32)[0].cpu().numpy()
+            jcount = np.minimum(count[:jc] * jt // T, jt).astype(np.uint64)  # the same distribution at the job's length
+
+            def wall(f):
+                t0 = time.perf_counter()
+                r = f()
+                return (time.perf_counter() - t0) * 1e3, r
+            job_uni = lambda: ctx.encode_job(xh)  # noqa: E731
+            job_var = lambda: ctx.encode_job(xh, count=jcount)  # noqa: E731
+            ru, rw = job_uni(), job_var()
+            assert int((rw[3] != 0).sum()) == 0
+            if equal:
+                assert all(a.tobytes() == b.tobytes() for a, b in zip(ru, rw))
+            for _ in range(args.warmup):
+                job_uni()
+                job_var()
+            tu, tw = [], []
+            for _ in range(args.runs):
+                tu.append(wall(job_uni)[0])
+                tw.append(wall(job_var)[0])
+            u, w = spread(tu), spread(tw)
+            report("encode_job int32 %dx%d" % (jc, jt), u, w, "; wall clock, pageable; counted: %.2f Gsamples/s of the samples below the counts"
+                   % (float(jcount.sum()) / (w["median_ms"] * 1e-3) / 1e9))
+            res["encode_job_i32"] = {"uniform": u, "counted": w, "channels": jc, "samples": jt}
+
     for name, count in dists:
         cd = torch.from_numpy(count).cuda()
         res = {"counts": name, "mean_count": float(count.mean()), "min_count": int(count.min())}
         say("counts %s: mean %.1f, smallest %d" % (name, count.mean(), count.min()))
         equal = bool((count == T).all())
+        int_parts(name, count, res)
+        if "float" not in args.parts:
+            results["distributions"].append(res)
+            continue
 
         # ---- (a) aggregate ----
         def agg_uni():
@@ -151,6 +223,8 @@ def main():
     # ---- (c) the writer: its text needs the room the encoder's slabs had ----
     del e_uni, e_var, a_uni, a_var
     torch.cuda.empty_cache()
+    if "csv" not in args.parts:
+        dists = []
     stride = (T * args.bytes_per_value + 16 + 15) // 16 * 16
     t_uni = (torch.zeros((Cn, stride), dtype=torch.uint8, device="cuda"), torch.zeros(Cn, dtype=torch.int64, device="cuda"), torch.zeros(Cn, dtype=torch.int32, device="cuda"))
     t_var = (torch.zeros((Cn, stride), dtype=torch.uint8, device="cuda"), torch.zeros(Cn, dtype=torch.int64, device="cuda"), torch.zeros(Cn, dtype=torch.int32, device="cuda"))
