@@ -102,6 +102,8 @@ _SIGNATURES = {
     "dega_hip_lzmh_encode_levels_f32_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _Z, C.c_uint, _Z, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "dega_hip_csv_read_dev": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, C.c_int, _P, _Z, _Z, _P, _P, _P]),
     "dega_hip_csv_read_host": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, C.c_int, _P, _Z, _Z, _P, _P]),
+    "dega_hip_csv_read_split_dev": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, C.c_int, _P, _Z, _Z, _P, _P, _Z, _P]),
+    "dega_hip_csv_read_split_block_bytes": (_Z, [_Z, _Z]),
     "dega_hip_lzmh_decode_f32_dev": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, _Z, C.c_int, _P, _Z, _Z, _P, _P, _P, _P]),
     "dega_hip_aggregate_levels_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _P, _Z, _P, _P, _P, _P, _P]),
     "dega_hip_encode_f32_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_float, C.c_int, C.c_int, _P, _Z, _P, _P, _P]),
@@ -176,6 +178,12 @@ def csv_line_max(decimals=2, column=1):
 def csv_worst_case_bytes(T, decimals=2, column=1):
     """A text stride that T readings can never overflow (dega_hip_csv_worst_case_bytes); 0 for options out of range."""
     return library().dega_hip_csv_worst_case_bytes(int(T), int(decimals), int(column))
+
+
+def csv_read_split_block_bytes(C_, stride):
+    """The block size csv_read(split="auto") takes for C_ channels of `stride` bytes (dega_hip_csv_read_split_block_bytes; no
+    GPU needed); 0 for a stride the reader refuses."""
+    return library().dega_hip_csv_read_split_block_bytes(int(C_), int(stride))
 
 
 def _separator(separator_char):
@@ -1025,11 +1033,14 @@ class Context(_JobCalls):
         return list(zip(out, bits, text_len, err))
 
     # ---- decode csv: text as float32 series, alone and behind LZMH -------------------------------------------------------
-    def csv_read(self, text, lens, max_T, column=1, separator_char=",", channels=None, ld=None, out=None):
+    def csv_read(self, text, lens, max_T, column=1, separator_char=",", channels=None, ld=None, out=None, split=None):
         """uint8 CUDA tensor [C, stride] with lens int64 [C] (what csv_write / lzmh_decode return) -> the reference's
         `decode csv` per channel (dega_hip_csv_read_dev): (v float32 [max_T, ld], count int64 [channels], err int32
         [channels]).  A channel with more than max_T values reports ERROR_MEMORY and the room it needs in count; one with
-        a selected field of 48 characters or more ERROR_INVALID_FORMAT.  Rows beyond a channel's count are unspecified."""
+        a selected field of 48 characters or more ERROR_INVALID_FORMAT.  Rows beyond a channel's count are unspecified.
+        split: None is that call; "auto" or a block size in bytes (a multiple of 16) splits every channel's text over lanes
+        (dega_hip_csv_read_split_dev; "auto" leaves the block size to csv_read_split_block_bytes) -- the same results, for
+        batches of few long channels."""
         import torch
         assert text.dim() == 2 and text.dtype == torch.uint8 and text.is_cuda and text.is_contiguous()
         assert lens.dtype == torch.int64 and lens.is_cuda and lens.is_contiguous() and lens.device == text.device
@@ -1044,6 +1055,13 @@ class Context(_JobCalls):
         assert out.shape[0] >= max_T and out.shape[1] == ld, "out must be [max_T, ld]"
         count = torch.zeros(Cn, dtype=torch.int64, device=text.device)
         err = torch.zeros(Cn, dtype=torch.int32, device=text.device)
+        if split is not None:
+            assert split == "auto" or (not isinstance(split, (str, bool)) and int(split) == split and split > 0), "split: None, \"auto\" or a block size in bytes"
+            ret = library().dega_hip_csv_read_split_dev(self._h, text.data_ptr(), stride, lens.data_ptr(), Cn, int(column), _separator(separator_char),
+                                                        out.data_ptr(), max_T, ld, count.data_ptr(), err.data_ptr(), 0 if split == "auto" else int(split),
+                                                        self._stream())
+            self._check(ret, "dega_hip_csv_read_split_dev")
+            return out, count, err
         ret = library().dega_hip_csv_read_dev(self._h, text.data_ptr(), stride, lens.data_ptr(), Cn, int(column), _separator(separator_char),
                                               out.data_ptr(), max_T, ld, count.data_ptr(), err.data_ptr(), self._stream())
         self._check(ret, "dega_hip_csv_read_dev")

@@ -15,6 +15,7 @@
 #include "aggregate_var_kernels.hpp"
 #include "csv_kernels.hpp"
 #include "csv_read_kernels.hpp"
+#include "csv_read_split_kernels.hpp"
 #include "transpose_kernels.hpp"
 
 #include <stdio.h>
@@ -61,8 +62,9 @@ struct dega_hip_ctx
   Pipeline *pipe;  // streams and buffers of the host-pointer entry points, created on first use
   // `sums`: the aggregated rows between the launches of the level calls; `text`: the text between the launches of
   // dega_hip_lzmh_encode_f32_dev / dega_hip_lzmh_encode_levels_f32_dev / dega_hip_lzmh_decode_f32_dev (in front of it
-  // the per-channel status and lengths, TextScratch).  Blocks they have outgrown are kept in `agg_retired`.
-  Scratch sums, text;
+  // the per-channel status and lengths, TextScratch); `split`: the [C][blocks] counts and first rows between the launches
+  // of dega_hip_csv_read_split_dev.  Blocks they have outgrown are kept in `agg_retired`.
+  Scratch sums, text, split;
   std::vector<void *> agg_retired;
 };
 
@@ -175,7 +177,7 @@ extern "C" void dega_hip_destroy(dega_hip_ctx *ctx)
   for (hipEvent_t e : ctx->ev_pool)
     (void)hipEventDestroy(e);
   (void)hipFree(ctx->div_magic);
-  for (Scratch *b : {&ctx->sums, &ctx->text})
+  for (Scratch *b : {&ctx->sums, &ctx->text, &ctx->split})
   {
     if (b->p != nullptr)
       (void)hipFree(b->p);
@@ -1613,6 +1615,53 @@ extern "C" int dega_hip_csv_read_dev(dega_hip_ctx *ctx, const uint8_t *text, siz
     return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: v_tc overlaps text", hipSuccess);
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
   return launch_csv_read(ctx, text, stride, len, C, column, separator_char, v_tc, max_T, ld, out_count, err, (hipStream_t)stream);
+}
+
+// ---- the same for few long channels: one channel's text split over lanes (csv_read_split_kernels.hpp) -----------------------
+
+extern "C" size_t dega_hip_csv_read_split_block_bytes(size_t C, size_t stride)
+{
+  return csv_read_split_block_bytes(C, stride);
+}
+
+extern "C" int dega_hip_csv_read_split_dev(dega_hip_ctx *ctx, const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column,
+                                           int separator_char, float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, int32_t *err,
+                                           size_t block_bytes, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  if ((ret = check_csv_read_options(ctx, C, column, separator_char, stride, ld)) != DEGA_OK)
+    return ret;
+  if (block_bytes == 0)
+    block_bytes = csv_read_split_block_bytes(C, stride);
+  if (block_bytes < 16 || (block_bytes & 15u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read split: block_bytes must be 0 or a multiple of 16 (at least 16)", hipSuccess);
+  if (!aligned16(text))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: text must be 16-byte aligned", hipSuccess);
+  if (C == 0)
+    return DEGA_OK;
+  if (text == nullptr || len == nullptr || ((uintptr_t)len & 7u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: text and len must be device arrays", hipSuccess);
+  if ((ret = check_csv_read_outputs(ctx, v_tc, max_T, out_count, err)) != DEGA_OK)
+    return ret;
+  if (max_T != 0 && ranges_overlap(text, C * stride, v_tc, image_bytes(max_T, ld, C)))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: v_tc overlaps text", hipSuccess);
+  const size_t blocks = csv_read_split_blocks(stride, block_bytes);
+  if (C > SIZE_MAX / sizeof(uint32_t) / blocks)
+    return fail(ctx, DEGA_ERROR_MEMORY, "csv read split: the blocks of the batch do not fit the address space", hipSuccess);
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  hipStream_t s = (hipStream_t)stream;
+  if ((ret = scratch_acquire(ctx, ctx->split, C * blocks * sizeof(uint32_t), s)) != DEGA_OK)
+    return ret;
+  const CsvReadArgs r = csv_read_args(text, stride, len, C, column, separator_char, v_tc, max_T, ld, out_count, err);
+  if (!launch(csv_read_split_args(r, block_bytes, (uint32_t *)ctx->split.p), OnStream{s}))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read split: too many blocks for one launch", hipSuccess); // (nothing launched)
+  const hipError_t launched = hipGetLastError();
+  ret = launched == hipSuccess ? DEGA_OK : fail(ctx, DEGA_ERROR_LIBRARY_CALL, "csv read split: launch", launched);
+  // (recorded whatever the launches said: the first may be on the stream and writes the scratch)
+  const int rel = scratch_release(ctx, ctx->split, s);
+  return rel != DEGA_OK ? rel : ret;
 }
 
 extern "C" int dega_hip_lzmh_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t text_stride,

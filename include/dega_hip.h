@@ -21,6 +21,8 @@
  *   dega_hip_csv_read_* / dega_hip_lzmh_decode_f32_*       ReadCSV (DCLib/src/csv.c:13-44, the same table row), alone or behind
  *                       LZMH: `decode csv`, the first stage of both of the study's chains, and `decode lzmh # decode csv`,
  *                       the inverse of its second.
+ *   dega_hip_csv_read_split_*                              ReadCSV again (DCLib/src/csv.c:13-44) with one channel's text split over
+ *                       lanes at line starts: the same results for batches of few long channels, one file per meter.
  *   dega_hip_*_var_dev (the block "ragged batches")         the same stages over channels of DIFFERENT lengths: what the
  *                       readers and decoders above deliver (a float matrix and a count per channel) goes into
  *                       aggregate, the DEGA float entry, `encode csv` and the LZMH chain as it is, every channel coded as
@@ -389,6 +391,31 @@ int dega_hip_csv_read_dev(dega_hip_ctx *ctx, const uint8_t *text, size_t stride,
    (max_T = 0) or from what wrote the text. */
 int dega_hip_csv_read_host(dega_hip_ctx *ctx, const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column, int separator_char,
                            float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, int32_t *err);
+/* dega_hip_csv_read_dev for few long channels: the same arguments, the same err[c], out_count[c] and rows below
+   min(out_count[c], max_T) of every channel, bit for bit (the three statuses above included); rows at or beyond a channel's
+   count are unspecified.  One channel's text is split over lanes, so that a single channel spreads over the whole device.
+   Ownership: a channel's len[c] bytes are cut into blocks of block_bytes, block b covering bytes [b * block_bytes,
+   (b + 1) * block_bytes), and a block owns exactly the lines that START inside it -- a line starts at byte 0 or at a byte
+   whose predecessor is '\n', where the reader's state is always column 1 and an empty field (csv.c:27-41).  A lane whose
+   block starts mid-line skips to just behind the first '\n' of its block (none, or one on the block's last byte: it owns
+   nothing), then runs csv.c:22-41 byte by byte, past its block's end if need be, and stops behind the first '\n' whose
+   successor lies in a later block or behind byte len[c] - 1, which is appended to a selected field and ends it whatever it
+   is (csv.c:23-26).  Three launches on `stream`, no synchronisation: a count of every block's values, a scan per channel
+   (each block's first row; the channel stops behind its first block with a field of 48 characters or more; out_count and
+   err), and the conversion, which is not launched for max_T = 0.  The counts between them live in a scratch of the context
+   with the protocol of the text scratch of dega_hip_lzmh_encode_f32_dev (grow-only, an event behind the last launch, a
+   call on another stream waits for it on the device).
+   block_bytes: 0 takes dega_hip_csv_read_split_block_bytes(C, stride); otherwise a multiple of 16, at least 16; a value
+   above stride is one block per channel.  Anything else, and everything dega_hip_csv_read_dev refuses, is
+   DEGA_ERROR_INVALID_VALUE before anything is launched; a scratch that cannot be had is DEGA_ERROR_MEMORY.  C = 0: nothing
+   is launched, DEGA_OK.  dega_hip_csv_read_dev, _host and dega_hip_lzmh_decode_f32_dev do not come here. */
+int dega_hip_csv_read_split_dev(dega_hip_ctx *ctx, const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column,
+                                int separator_char, float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, int32_t *err,
+                                size_t block_bytes, void *stream);
+/* the library's choice of block_bytes for a batch (pure host code, no GPU): a multiple of 16 in 16 .. max(16, stride) -- the
+   largest block that still gives the batch enough (channel, block) pairs to fill the device, not below a floor; for a fixed
+   stride it does not decrease as C grows.  0 for a stride that dega_hip_csv_read_dev refuses. */
+size_t dega_hip_csv_read_split_block_bytes(size_t C, size_t stride);
 /* `decode lzmh # decode csv` per channel on `stream`, no synchronisation: the inverse of dega_hip_lzmh_encode_f32_dev.
    dega_hip_lzmh_decode_dev, left as it is, writes into the context's text scratch (text_stride bytes per channel, a
    multiple of 16; its protocol and its event are those of dega_hip_lzmh_encode_f32_dev), the reader runs over that text,

@@ -14,7 +14,14 @@ What (a) reads back is compared with the floats the text was written from, bit f
 beside (a): text bytes read plus float bytes written over the float4-copy yardstick, and the issue floor from
 --instr-per-byte and --instr-per-value (the kernel's instructions per text byte and per value, counted in its ISA) x 4.3
 cycles at the waves per SIMD the batch gives.  Prints one line per measurement and a JSON summary per channel count; --out
-also writes them to a file."""
+also writes them to a file.
+
+    python tools/csvreadbench.py --split [--channels 1 16 256 4096 65536] [--out profiles/csv_read_split_bench.txt]
+
+measures instead dega_hip_csv_read_split_dev (one channel's text split over lanes) at block_bytes 64, 256, 1 024, 4 096,
+16 384 and at the library's choice, alternating run by run with (a), the existing kernel, in the same session.  Every split
+result is compared bit for bit with the floats the text was written from before anything is timed.  One line per
+candidate (median, fastest .. slowest, the ratio of (a)'s median to it) and a JSON summary per channel count."""
 import argparse
 import json
 import os
@@ -137,9 +144,83 @@ def one_size(dca, ctx, Cn, T, args, say):
     return res
 
 
+SPLIT_BLOCKS = (64, 256, 1024, 4096, 16384)
+
+
+def one_size_split(dca, ctx, Cn, T, args, say):
+    import torch
+    L = dca.library()
+    s = ctx._stream()
+    x = ctx.synth(Cn, T, seed=1234, S=50)
+    v = torch.empty((T, Cn), dtype=torch.float32, device="cuda")
+    hundred = torch.full((), 100.0, dtype=torch.float64, device="cuda")
+    for t0 in range(0, T, 4096):
+        v[t0:t0 + 4096] = (x[t0:t0 + 4096].to(torch.float64) / hundred).to(torch.float32)
+    del x
+    stride = (T * 9 + 16 + 15) // 16 * 16
+    text = torch.empty((Cn, stride), dtype=torch.uint8, device="cuda")
+    lens = torch.zeros(Cn, dtype=torch.int64, device="cuda")
+    err = torch.zeros(Cn, dtype=torch.int32, device="cuda")
+    back = torch.empty((T, Cn), dtype=torch.float32, device="cuda")
+    count = torch.zeros(Cn, dtype=torch.int64, device="cuda")
+    assert L.dega_hip_csv_write_dev(ctx._h, v.data_ptr(), Cn, T, Cn, 2, 1, 44, text.data_ptr(), stride, lens.data_ptr(), err.data_ptr(), s) == 0
+    torch.cuda.synchronize()
+    assert int((err != 0).sum().item()) == 0
+    text_bytes = int(lens.sum().item())
+    chosen = dca.csv_read_split_block_bytes(Cn, stride)
+
+    def read():
+        assert L.dega_hip_csv_read_dev(ctx._h, text.data_ptr(), stride, lens.data_ptr(), Cn, 1, 44, back.data_ptr(), T, Cn, count.data_ptr(), err.data_ptr(), s) == 0
+
+    def split(block_bytes):
+        def fn():
+            assert L.dega_hip_csv_read_split_dev(ctx._h, text.data_ptr(), stride, lens.data_ptr(), Cn, 1, 44, back.data_ptr(), T, Cn, count.data_ptr(),
+                                                 err.data_ptr(), block_bytes, s) == 0
+        return fn
+
+    def checked(what):
+        torch.cuda.synchronize()
+        assert int((err != 0).sum().item()) == 0 and int((count != T).sum().item()) == 0, what
+        assert all(torch.equal(back[t0:t0 + 4096].view(torch.int32), v[t0:t0 + 4096].view(torch.int32)) for t0 in range(0, T, 4096)), what
+
+    fns = {"csv_read_dev": read}
+    for B in SPLIT_BLOCKS:
+        fns["csv_read_split_dev block_bytes=%d" % B] = split(B)
+    fns["csv_read_split_dev library's choice (%d)" % chosen] = split(0)
+    for k, fn in fns.items():  # right before it is timed
+        back.zero_()
+        count.zero_()
+        fn()
+        checked(k + " does not return the floats the text was written from")
+    for _ in range(args.warmup):
+        for fn in fns.values():
+            fn()
+    ms = {k: [] for k in fns}
+    for _ in range(args.runs):  # alternating run by run
+        for k, fn in fns.items():
+            ms[k].append(event_ms(fn))
+    res = {"channels": Cn, "samples": T, "warmup": args.warmup, "stride": stride, "text_bytes": text_bytes, "library_block_bytes": chosen,
+           "library_pairs": Cn * ((stride + chosen - 1) // chosen)}
+    say("%d channels x %d readings, %d text bytes, stride %d; the library's choice of block_bytes: %d (%d pairs)"
+        % (Cn, T, text_bytes, stride, chosen, res["library_pairs"]))
+    base = None
+    for k in fns:
+        x = res[k] = spread(ms[k])
+        base = x if base is None else base
+        say("%-46s median %10.3f ms  fastest %10.3f .. slowest %10.3f  (%d runs)  existing / this = %8.3f"
+            % (k, x["median_ms"], x["fastest_ms"], x["slowest_ms"], x["runs"], base["median_ms"] / x["median_ms"]))
+    mine = res["csv_read_split_dev library's choice (%d)" % chosen]
+    res["existing_over_library_choice"] = round(base["median_ms"] / mine["median_ms"], 3)
+    res["ranges_apart"] = mine["slowest_ms"] < base["fastest_ms"]
+    say("library's choice: slowest %.3f ms %s the existing kernel's fastest %.3f ms" % (mine["slowest_ms"], "<" if res["ranges_apart"] else ">=", base["fastest_ms"]))
+    say(json.dumps(res))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--channels", type=int, nargs="+", default=[256, 65536])
+    ap.add_argument("--channels", type=int, nargs="+", default=None, help="default 256 65536; with --split 1 16 256 4096 65536")
+    ap.add_argument("--split", action="store_true", help="measure dega_hip_csv_read_split_dev against the existing kernel instead")
     ap.add_argument("--samples", type=int, default=86400)
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -155,9 +236,11 @@ def main():
     def say(line):
         print(line, flush=True)
         lines.append(line)
+    if args.channels is None:
+        args.channels = [1, 16, 256, 4096, 65536] if args.split else [256, 65536]
     for Cn in args.channels:
         ctx = dca.Context(0)
-        one_size(dca, ctx, Cn, args.samples, args, say)
+        (one_size_split if args.split else one_size)(dca, ctx, Cn, args.samples, args, say)
         ctx.close()
         torch.cuda.empty_cache()
     if args.out:
