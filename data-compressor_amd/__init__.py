@@ -109,6 +109,8 @@ _SIGNATURES = {
     "dega_hip_encode_f32_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_float, C.c_int, C.c_int, _P, _Z, _P, _P, _P]),
     "dega_hip_encode_levels_f32_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _P, _Z, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "dega_hip_csv_write_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_uint, _Z, C.c_int, _P, _Z, _P, _P, _P]),
+    "dega_hip_csv_write_split_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_uint, _Z, C.c_int, _P, _Z, _P, _P, _Z, _P]),
+    "dega_hip_csv_write_split_block_rows": (_Z, [_Z, _Z]),
     "dega_hip_lzmh_encode_levels_f32_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _P, _Z, C.c_uint, _Z, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dega_hip_encode_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_int, C.c_int, C.c_int, _P, _Z, _P, _P, _P]),
     "dega_hip_encode64_var_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, C.c_int, C.c_int, _P, _Z, _P, _P, _P]),
@@ -184,6 +186,12 @@ def csv_read_split_block_bytes(C_, stride):
     """The block size csv_read(split="auto") takes for C_ channels of `stride` bytes (dega_hip_csv_read_split_block_bytes; no
     GPU needed); 0 for a stride the reader refuses."""
     return library().dega_hip_csv_read_split_block_bytes(int(C_), int(stride))
+
+
+def csv_write_split_block_rows(C_, T):
+    """The rows per block csv_write(split="auto") takes for C_ channels of T readings (dega_hip_csv_write_split_block_rows; no
+    GPU needed); 0 for a T the counted form refuses."""
+    return library().dega_hip_csv_write_split_block_rows(int(C_), int(T))
 
 
 def _separator(separator_char):
@@ -925,12 +933,15 @@ class Context(_JobCalls):
         return out, lens, err
 
     # ---- encode csv: float32 series as text, alone and in front of LZMH ------------------------------------------------
-    def csv_write(self, v_tc, decimals=2, column=1, separator_char=",", stride=None, channels=None, out=None, count=None):
+    def csv_write(self, v_tc, decimals=2, column=1, separator_char=",", stride=None, channels=None, out=None, count=None, split=None):
         """float32 CUDA tensor [T, ld] -> the reference's `encode csv` text per channel (dega_hip_csv_write_dev):
         (text uint8 [channels, stride], lens int64 [channels], err int32 [channels]).  stride (a multiple of 16) defaults
         to csv_worst_case_bytes; a channel whose text + 16 bytes does not fit it reports ERROR_MEMORY and length 0.
         count (int64 CUDA tensor, one per channel): a ragged batch (dega_hip_csv_write_var_dev) -- channel c's text is its
-        first count[c] readings; count[c] > T reports ERROR_INVALID_VALUE and length 0."""
+        first count[c] readings; count[c] > T reports ERROR_INVALID_VALUE and length 0.
+        split: None is those calls; "auto" or a number of rows per block splits every channel's rows over lanes
+        (dega_hip_csv_write_split_dev, with count as well; "auto" leaves the block to csv_write_split_block_rows) -- the same
+        lens, err and bytes below lens, for batches of few long channels; bytes at or beyond lens[c] are then left untouched."""
         import torch
         assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
         T, ld = v_tc.shape
@@ -945,6 +956,13 @@ class Context(_JobCalls):
         assert out.shape[0] >= Cn and out.shape[1] == stride, "out must be [channels, stride]"
         lens = torch.zeros(Cn, dtype=torch.int64, device=v_tc.device)
         err = torch.zeros(Cn, dtype=torch.int32, device=v_tc.device)
+        if split is not None:
+            assert split == "auto" or (not isinstance(split, (str, bool)) and int(split) == split and split > 0), "split: None, \"auto\" or rows per block"
+            ret = library().dega_hip_csv_write_split_dev(self._h, v_tc.data_ptr(), Cn, T, ld, None if count is None else _count_ptr(count, Cn, v_tc.device),
+                                                         int(decimals), int(column), _separator(separator_char), out.data_ptr(), stride, lens.data_ptr(),
+                                                         err.data_ptr(), 0 if split == "auto" else int(split), self._stream())
+            self._check(ret, "dega_hip_csv_write_split_dev")
+            return out[:Cn], lens, err
         if count is not None:
             ret = library().dega_hip_csv_write_var_dev(self._h, v_tc.data_ptr(), Cn, T, ld, _count_ptr(count, Cn, v_tc.device), int(decimals), int(column),
                                                        _separator(separator_char), out.data_ptr(), stride, lens.data_ptr(), err.data_ptr(), self._stream())

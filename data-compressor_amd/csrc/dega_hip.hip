@@ -16,6 +16,7 @@
 #include "csv_kernels.hpp"
 #include "csv_read_kernels.hpp"
 #include "csv_read_split_kernels.hpp"
+#include "csv_write_split_kernels.hpp"
 #include "transpose_kernels.hpp"
 
 #include <stdio.h>
@@ -63,8 +64,9 @@ struct dega_hip_ctx
   // `sums`: the aggregated rows between the launches of the level calls; `text`: the text between the launches of
   // dega_hip_lzmh_encode_f32_dev / dega_hip_lzmh_encode_levels_f32_dev / dega_hip_lzmh_decode_f32_dev (in front of it
   // the per-channel status and lengths, TextScratch); `split`: the [C][blocks] counts and first rows between the launches
-  // of dega_hip_csv_read_split_dev.  Blocks they have outgrown are kept in `agg_retired`.
-  Scratch sums, text, split;
+  // of dega_hip_csv_read_split_dev; `wsplit`: the [C][blocks] lengths and byte offsets between the launches of
+  // dega_hip_csv_write_split_dev.  Blocks they have outgrown are kept in `agg_retired`.
+  Scratch sums, text, split, wsplit;
   std::vector<void *> agg_retired;
 };
 
@@ -177,7 +179,7 @@ extern "C" void dega_hip_destroy(dega_hip_ctx *ctx)
   for (hipEvent_t e : ctx->ev_pool)
     (void)hipEventDestroy(e);
   (void)hipFree(ctx->div_magic);
-  for (Scratch *b : {&ctx->sums, &ctx->text, &ctx->split})
+  for (Scratch *b : {&ctx->sums, &ctx->text, &ctx->split, &ctx->wsplit})
   {
     if (b->p != nullptr)
       (void)hipFree(b->p);
@@ -1356,6 +1358,63 @@ extern "C" int dega_hip_csv_write_var_dev(dega_hip_ctx *ctx, const float *v_tc, 
                                           size_t column, int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, void *stream)
 {
   return csv_write(ctx, v_tc, C, T, ld, true, count, decimals, column, separator_char, out, stride, out_len, err, (hipStream_t)stream);
+}
+
+// ---- the same for few long channels: one channel's rows split over lanes (csv_write_split_kernels.hpp) -----------------------
+
+extern "C" size_t dega_hip_csv_write_split_block_rows(size_t C, size_t T)
+{
+  return csv_write_split_block_rows(C, T);
+}
+
+extern "C" int dega_hip_csv_write_split_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, unsigned decimals,
+                                            size_t column, int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err,
+                                            size_t block_rows, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  // the refusals of csv_write, in its order
+  if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, stride)) != DEGA_OK)
+    return ret;
+  if (!aligned16(out))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out must be 16-byte aligned", hipSuccess);
+  if (C == 0)
+    return DEGA_OK;
+  if (out == nullptr || out_len == nullptr || err == nullptr || ((uintptr_t)out_len & 7u) != 0 || ((uintptr_t)err & 3u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out, out_len and err must be device arrays", hipSuccess);
+  if (count != nullptr && (ret = check_counts(ctx, C, T, count, nullptr, 0, err)) != DEGA_OK)
+    return ret;
+  if (T != 0 && !f32_array(v_tc))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: v_tc must be a float32 device array", hipSuccess);
+  if (T != 0 && ranges_overlap(out, C * stride, v_tc, image_bytes(T, ld, C)))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out overlaps v_tc", hipSuccess);
+  if (block_rows == 0 && (block_rows = csv_write_split_block_rows(C, T)) == 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv write split: 2^32 rows and more need a block_rows of the caller's", hipSuccess);
+  const size_t blocks = csv_write_split_blocks(T, block_rows);
+  if (blocks > 0xFFFFFFFFu || csv_write_split_grid(C, blocks) == 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv write split: too many blocks for one launch", hipSuccess);
+  if (C > SIZE_MAX / sizeof(uint32_t) / blocks)
+    return fail(ctx, DEGA_ERROR_MEMORY, "csv write split: the blocks of the batch do not fit the address space", hipSuccess);
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  hipStream_t s = (hipStream_t)stream;
+  if (T == 0 && count == nullptr) // no reading, no text: lengths 0, nothing launched
+  {
+    HIP_TRY(ctx, hipMemsetAsync(out_len, 0, C * sizeof(uint64_t), s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipMemsetAsync(err, 0, C * sizeof(int32_t), s), DEGA_ERROR_LIBRARY_CALL);
+    return DEGA_OK;
+  }
+  // (a counted batch still launches length and scan at T = 0, as the unsplit call does: a count above it is theirs to report)
+  if ((ret = scratch_acquire(ctx, ctx->wsplit, C * blocks * sizeof(uint32_t), s)) != DEGA_OK)
+    return ret;
+  const CsvArgs a = csv_args(v_tc, C, T, ld, decimals, column, separator_char, out, stride, out_len, err, count);
+  if (!launch(csv_write_split_args(a, block_rows, (uint32_t *)ctx->wsplit.p), OnStream{s}))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv write split: too many blocks for one launch", hipSuccess); // (nothing launched)
+  const hipError_t launched = hipGetLastError();
+  ret = launched == hipSuccess ? DEGA_OK : fail(ctx, DEGA_ERROR_LIBRARY_CALL, "csv write split: launch", launched);
+  // (recorded whatever the launches said: the first may be on the stream and writes the scratch)
+  const int rel = scratch_release(ctx, ctx->wsplit, s);
+  return rel != DEGA_OK ? rel : ret;
 }
 
 static size_t round16(size_t n)

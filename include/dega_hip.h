@@ -23,6 +23,8 @@
  *                       the inverse of its second.
  *   dega_hip_csv_read_split_*                              ReadCSV again (DCLib/src/csv.c:13-44) with one channel's text split over
  *                       lanes at line starts: the same results for batches of few long channels, one file per meter.
+ *   dega_hip_csv_write_split_*                             WriteCSV again (DCLib/src/csv.c:46-65) with one channel's rows split over
+ *                       lanes: the same text for batches of few long channels, one file per meter.
  *   dega_hip_*_var_dev (the block "ragged batches")         the same stages over channels of DIFFERENT lengths: what the
  *                       readers and decoders above deliver (a float matrix and a count per channel) goes into
  *                       aggregate, the DEGA float entry, `encode csv` and the LZMH chain as it is, every channel coded as
@@ -486,6 +488,29 @@ int dega_hip_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const float *v_tc, siz
 /* dega_hip_csv_write_dev over a ragged batch: channel c's text is its first count[c] readings. */
 int dega_hip_csv_write_var_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count, unsigned decimals,
                                size_t column, int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err, void *stream);
+/* dega_hip_csv_write_dev (count == NULL) and dega_hip_csv_write_var_dev (count: channel c is its first count[c] readings,
+   count[c] > T is DEGA_ERROR_INVALID_VALUE and length 0) for few long channels: the same out_len[c], err[c] and bytes
+   [0, out_len[c]) of every row, byte for byte.  The unit of work is a (channel, block of rows) pair: block b of channel c
+   owns rows [b * block_rows, min((b + 1) * block_rows, n_c)), n_c being T or count[c].  Three launches on `stream`, no
+   synchronisation: the lengths of every block's lines, per channel their exclusive prefix (with out_len and err; a channel
+   fits iff text + 16 <= stride, else DEGA_ERROR_MEMORY and length 0), and the text, every block at its byte offset -- not
+   launched for T = 0.  Stricter than the unsplit call: NO byte of `out` at or beyond out_len[c] is written, and nothing at
+   all of a channel that reports an error.  The words between the launches live in a scratch of the context with the
+   protocol of the text scratch of dega_hip_lzmh_encode_f32_dev (grow-only, an event behind the last launch, a call on
+   another stream waits for it on the device).
+   block_rows: 0 takes dega_hip_csv_write_split_block_rows(C, T); any value from 1 on is legal, one at or above T is one
+   block per channel.  Everything dega_hip_csv_write_dev / _var_dev refuse, more than 2^32 - 1 blocks per channel, more
+   pairs than one launch takes, and block_rows = 0 at T >= 2^32 are DEGA_ERROR_INVALID_VALUE before anything is launched; a
+   scratch that cannot be had is DEGA_ERROR_MEMORY.  C = 0: nothing is launched, DEGA_OK.  T = 0: the lengths are 0 and
+   nothing is launched (with a count, the two launches that report count[c] > 0).  dega_hip_csv_write_dev, _host, _var_dev
+   and the dega_hip_lzmh_encode*_f32* chains do not come here. */
+int dega_hip_csv_write_split_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count /* may be NULL */,
+                                 unsigned decimals, size_t column, int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err,
+                                 size_t block_rows, void *stream);
+/* the library's choice of block_rows for a batch (pure host code, no GPU): within 1 .. max(1, T) -- the largest block that
+   still gives the batch enough (channel, block) pairs to fill the device, not below a floor; for a fixed T it does not
+   decrease as C grows.  0 for a T that dega_hip_csv_write_var_dev refuses (2^32 and more). */
+size_t dega_hip_csv_write_split_block_rows(size_t C, size_t T);
 /* dega_hip_lzmh_encode_levels_f32_dev over a ragged batch -- the chain WITH `aggregate` in it, as its twin: every level,
    num_values 1 included, through the counted aggregate kernel, then per level the counted renderer, the LZMH encoder and the
    status launches.  out_count[k] is required (level k's values per channel: what dega_hip_lzmh_decode_f32_dev reports

@@ -13,7 +13,15 @@ Then the stages around it: (d) dega_hip_lzmh_encode_dev over the produced text (
 dega_hip_decode_f32_dev over the DEGA streams of the same readings (the stage it follows in the decode direction).
 The kernel's two bounds are printed beside (a)/(b): bytes read plus text bytes written over the float4-copy yardstick, and
 the issue floor from --valu-per-value (the kernel's VALU instructions per value, counted in its ISA) x 4.3 cycles x T at
-one wave per SIMD.  Prints one line per measurement and a JSON summary at the end."""
+one wave per SIMD.  Prints one line per measurement and a JSON summary at the end.
+
+    python tools/csvbench.py --split [--split-channels 1,16,256,4096,65536] [--split-block-rows 1,4,...] [--samples 86400]
+
+The sweep of the split writer (dega_hip_csv_write_split_dev): per channel count one batch of the same readings, and per
+block_rows -- the library's choice (0) first, then the list -- the split call beside dega_hip_csv_write_dev on the same
+data, alternating run by run; every split result is compared with the unsplit bytes, lengths and status before anything is
+timed.  Cells with more than --split-max-pairs (channel, block) pairs are left out.  One line per cell: median, fastest and
+slowest of both."""
 import argparse
 import json
 import os
@@ -48,6 +56,71 @@ def show(label, x, extra=""):
           % (label, x["median_ms"], x["fastest_ms"], x["p90_ms"], x["slowest_ms"], x["runs"], extra))
 
 
+def split_sweep(args):
+    import torch
+    from __graft_entry__ import load_package
+    dca = load_package()
+    L = dca.library()
+    ctx = dca.Context(0)
+    s = ctx._stream()
+    T = args.samples
+    stride = (T * 9 + 16 + 15) // 16 * 16
+    res = {"samples": T, "cells": []}
+    for Cn in [int(c) for c in args.split_channels.split(",")]:
+        x = ctx.synth(Cn, T, seed=1234, S=50)  # centi-units, the workload of bench.py
+        v = torch.empty((T, Cn), dtype=torch.float32, device="cuda")
+        for t0 in range(0, T, 4096):
+            v[t0:t0 + 4096] = x[t0:t0 + 4096].to(torch.float32) / 100.0
+        del x
+        text = torch.empty((Cn, stride), dtype=torch.uint8, device="cuda")
+        text0 = torch.empty((Cn, stride), dtype=torch.uint8, device="cuda")
+        lens, lens0 = torch.zeros(Cn, dtype=torch.int64, device="cuda"), torch.zeros(Cn, dtype=torch.int64, device="cuda")
+        err, err0 = torch.zeros(Cn, dtype=torch.int32, device="cuda"), torch.zeros(Cn, dtype=torch.int32, device="cuda")
+
+        def unsplit():
+            assert L.dega_hip_csv_write_dev(ctx._h, v.data_ptr(), Cn, T, Cn, 2, 1, 44, text0.data_ptr(), stride, lens0.data_ptr(), err0.data_ptr(), s) == 0
+
+        unsplit()
+        torch.cuda.synchronize()
+        assert int((err0 != 0).sum().item()) == 0
+        chosen = dca.csv_write_split_block_rows(Cn, T)
+        print("%d channels x %d readings, %d text bytes; the library's block_rows: %d" % (Cn, T, int(lens0.sum().item()), chosen))
+        for R in [0] + [int(r) for r in args.split_block_rows.split(",")]:
+            rows = chosen if R == 0 else min(R, T)
+            pairs = Cn * (-(-T // rows))
+            if pairs > args.split_max_pairs:
+                print("  block_rows %6d: %d pairs, left out" % (rows, pairs))
+                continue
+
+            def split():
+                assert L.dega_hip_csv_write_split_dev(ctx._h, v.data_ptr(), Cn, T, Cn, None, 2, 1, 44, text.data_ptr(), stride, lens.data_ptr(), err.data_ptr(),
+                                                      R, s) == 0
+
+            text.fill_(0xEE)
+            split()
+            torch.cuda.synchronize()
+            assert torch.equal(lens, lens0) and torch.equal(err, err0), "the split writer disagrees on the lengths"
+            for c0 in range(0, Cn, 256):  # (the benchmark's channels differ in length by a few bytes)
+                n = int(lens0[c0:c0 + 256].min())
+                assert torch.equal(text[c0:c0 + 256, :n], text0[c0:c0 + 256, :n]), "the split writer disagrees on the text"
+                assert bool((text[c0:c0 + 256, int(lens0[c0:c0 + 256].max()):] == 0xEE).all()), "the split writer wrote behind the text"
+            first = event_ms(split)
+            runs = 30 if first < 5.0 else (10 if first < 60.0 else 3)
+            a, b = [], []
+            for _ in range(runs):  # alternating run by run
+                a.append(event_ms(split))
+                b.append(event_ms(unsplit))
+            cell = {"channels": Cn, "block_rows": rows, "library_choice": R == 0, "pairs": pairs, "split": spread(a), "unsplit": spread(b)}
+            res["cells"].append(cell)
+            print("  block_rows %6d%s %10d pairs  split median %9.3f fastest %9.3f slowest %9.3f | unsplit median %9.3f fastest %9.3f slowest %9.3f ms  (%d runs)  %.2fx"
+                  % (rows, "*" if R == 0 else " ", pairs, cell["split"]["median_ms"], cell["split"]["fastest_ms"], cell["split"]["slowest_ms"],
+                     cell["unsplit"]["median_ms"], cell["unsplit"]["fastest_ms"], cell["unsplit"]["slowest_ms"], runs,
+                     cell["unsplit"]["median_ms"] / cell["split"]["median_ms"]), flush=True)
+        del v, text, text0
+    print(json.dumps(res))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--channels", type=int, default=65536)
@@ -56,7 +129,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--lzmh-runs", type=int, default=2, help="timed runs of the LZMH encoder over the text (seconds each at full size)")
     ap.add_argument("--valu-per-value", type=float, default=0.0, help="VALU instructions per value of the kernel's loop, for the issue floor")
+    ap.add_argument("--split", action="store_true", help="the sweep of the split writer instead (see the top)")
+    ap.add_argument("--split-channels", default="1,16,256,4096,65536")
+    ap.add_argument("--split-block-rows", default="1,4,16,64,256,1024,4096,21600,86400")
+    ap.add_argument("--split-max-pairs", type=int, default=400 << 20)
     args = ap.parse_args()
+    if args.split:
+        return split_sweep(args)
     import torch
     from __graft_entry__ import load_package
     dca = load_package()
