@@ -1197,6 +1197,22 @@ static bool aligned16(const void *p)
   return ((uintptr_t)p & 15u) == 0;
 }
 
+// What the LZMH entry points refuse about their row sizes, for device and host pointers alike (`aligned`: the device
+// arrays are on the kernels' boundaries -- the caller's, or a slot's own)
+static int check_lzmh_encode(dega_hip_ctx *ctx, size_t stride, size_t cap, bool aligned)
+{
+  if (stride == 0 || (stride & 15u) != 0 || (cap & 15u) != 0 || cap < 48 || stride > 0x7FFFFFF0u || !aligned)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode: stride/cap must be multiples of 16 (cap >= 48), buffers 16-byte aligned", hipSuccess);
+  return DEGA_OK;
+}
+
+static int check_lzmh_decode(dega_hip_ctx *ctx, size_t cap, size_t stride, bool aligned)
+{
+  if (cap < 4 || (cap & 3u) != 0 || stride < 8 || (stride & 7u) != 0 || !aligned)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh decode: cap must be a multiple of 4, stride a multiple of 8", hipSuccess);
+  return DEGA_OK;
+}
+
 // When does a channel fit its slab?  With F the full 32-bit words of its stream and W = 4 * ceil(bits / 32) its bytes in whole
 // words, lzmh_coding_wave stores F / 4 blocks of 16 bytes, the k-th at byte 16 * k and only if 16 * k + 32 <= cap, and then,
 // in finish, the F % 4 words left and the partial one, only if 4 * (F + 1) <= cap.  16 * (F / 4) <= 4 * F <= W, so
@@ -1210,8 +1226,9 @@ extern "C" int dega_hip_lzmh_encode_dev(dega_hip_ctx *ctx, const uint8_t *in, si
 {
   if (ctx == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
-  if (stride == 0 || (stride & 15u) != 0 || (cap & 15u) != 0 || cap < 48 || stride > 0x7FFFFFF0u || !aligned16(in) || !aligned16(out))
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode: stride/cap must be multiples of 16 (cap >= 48), buffers 16-byte aligned", hipSuccess);
+  int ret;
+  if ((ret = check_lzmh_encode(ctx, stride, cap, aligned16(in) && aligned16(out))) != DEGA_OK)
+    return ret;
   if (C == 0)
     return DEGA_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
@@ -1230,8 +1247,9 @@ extern "C" int dega_hip_lzmh_decode_dev(dega_hip_ctx *ctx, const uint8_t *in, si
 {
   if (ctx == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
-  if (cap < 4 || (cap & 3u) != 0 || stride < 8 || (stride & 7u) != 0 || ((uintptr_t)in & 3u) != 0 || ((uintptr_t)out & 7u) != 0)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh decode: cap must be a multiple of 4, stride a multiple of 8", hipSuccess);
+  int ret;
+  if ((ret = check_lzmh_decode(ctx, cap, stride, ((uintptr_t)in & 3u) == 0 && ((uintptr_t)out & 7u) == 0)) != DEGA_OK)
+    return ret;
   if (C == 0)
     return DEGA_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
@@ -1762,121 +1780,3 @@ extern "C" int dega_hip_lzmh_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in
 
 // ---- host-pointer entry points: the pipeline and the multi-device group ------------------------------------------------------
 #include "dega_pipeline.hpp"
-
-// float32 rows in host memory -> their text in host memory, synchronous, in the manner of dega_hip_aggregate_host: chunks of
-// channels through the context's first slot (upload, one launch, download), as many channels at a time as keep the
-// readings and their text under a gigabyte
-extern "C" int dega_hip_csv_write_host(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column,
-                                       int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err)
-{
-  if (ctx == nullptr)
-    return DEGA_ERROR_INVALID_VALUE;
-  int ret;
-  if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, stride)) != DEGA_OK)
-    return ret;
-  if (C == 0)
-    return DEGA_OK;
-  if (out == nullptr || out_len == nullptr || err == nullptr)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out, out_len and err must be arrays", hipSuccess);
-  if (T == 0)
-  {
-    memset(out_len, 0, C * sizeof(uint64_t));
-    memset(err, 0, C * sizeof(int32_t));
-    return DEGA_OK;
-  }
-  if (v_tc == nullptr)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: v_tc must be a float32 array", hipSuccess);
-  Pipeline *pl;
-  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  if ((ret = pipeline_get(ctx, &pl)) != DEGA_OK)
-    return ret;
-  Slot &sl = pl->slot[0];
-  if ((ret = slot_stream(ctx, sl)) != DEGA_OK)
-    return ret;
-  const size_t per_channel = T * sizeof(float) + stride;
-  size_t step = std::max<size_t>(1, ((size_t)1 << 30) / per_channel);
-  if (step >= 4)
-    step = step / 4 * 4;
-  const bool in_pinned = is_pinned(v_tc), out_pinned = is_pinned(out), len_pinned = is_pinned(out_len), err_pinned = is_pinned(err);
-  for (size_t c0 = 0; c0 < C; c0 += step)
-  {
-    const size_t n = std::min(step, C - c0);
-    HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, sl.c.need(n * T * sizeof(float) + 64), DEGA_ERROR_MEMORY);
-    HIP_TRY(ctx, sl.a.need(n * stride + 64), DEGA_ERROR_MEMORY);
-    HIP_TRY(ctx, sl.meta.need(n * (sizeof(uint64_t) + sizeof(int32_t)) + 64), DEGA_ERROR_MEMORY);
-    uint64_t *const d_len = (uint64_t *)sl.meta.p;
-    int32_t *const d_err = (int32_t *)((uint8_t *)sl.meta.p + n * sizeof(uint64_t));
-    HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, (const uint8_t *)(v_tc + c0), ld * sizeof(float), n * sizeof(float), T, in_pinned), DEGA_ERROR_LIBRARY_CALL);
-    if ((ret = launch_csv(ctx, (const float *)sl.c.p, n, T, n, decimals, column, separator_char, (uint8_t *)sl.a.p, stride, d_len, d_err, sl.s)) != DEGA_OK)
-      return ret;
-    HIP_TRY(ctx, rows_to_host(pl, sl.s, out + c0 * stride, stride, sl.a.p, stride, n, out_pinned), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(out_len + c0), n * sizeof(uint64_t), d_len, n * sizeof(uint64_t), 1, len_pinned), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(err + c0), n * sizeof(int32_t), d_err, n * sizeof(int32_t), 1, err_pinned), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-  return DEGA_OK;
-}
-
-// Text rows in host memory -> float32 rows in host memory, synchronous, as plain as dega_hip_csv_write_host: chunks of
-// channels through the context's first slot (upload, one launch, download), as many channels at a time as keep the text
-// and its values under a gigabyte
-extern "C" int dega_hip_csv_read_host(dega_hip_ctx *ctx, const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column,
-                                      int separator_char, float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, int32_t *err)
-{
-  if (ctx == nullptr)
-    return DEGA_ERROR_INVALID_VALUE;
-  int ret;
-  if ((ret = check_csv_read_options(ctx, C, column, separator_char, stride, ld)) != DEGA_OK)
-    return ret;
-  if (C == 0)
-    return DEGA_OK;
-  if (text == nullptr || len == nullptr)
-    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: text and len must be arrays", hipSuccess);
-  if ((ret = check_csv_read_outputs(ctx, v_tc, max_T, out_count, err)) != DEGA_OK)
-    return ret;
-  for (size_t c = 0; c < C; c++)
-    if (len[c] > stride)
-      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: a len[c] is larger than stride", hipSuccess);
-  Pipeline *pl;
-  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  if ((ret = pipeline_get(ctx, &pl)) != DEGA_OK)
-    return ret;
-  Slot &sl = pl->slot[0];
-  if ((ret = slot_stream(ctx, sl)) != DEGA_OK)
-    return ret;
-  // a text of `stride` bytes holds at most `stride` values: more room than that is never used, and sizes stay far from wrapping
-  const size_t rows = std::min(max_T, stride);
-  const size_t per_channel = rows * sizeof(float) + stride;
-  size_t step = std::max<size_t>(1, ((size_t)1 << 30) / per_channel);
-  if (step >= 4)
-    step = step / 4 * 4;
-  const bool in_pinned = is_pinned(text), len_pinned = is_pinned(len), out_pinned = is_pinned(v_tc), count_pinned = is_pinned(out_count),
-             err_pinned = is_pinned(err);
-  for (size_t c0 = 0; c0 < C; c0 += step)
-  {
-    const size_t n = std::min(step, C - c0);
-    HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, sl.a.need(n * stride + 64), DEGA_ERROR_MEMORY);
-    HIP_TRY(ctx, sl.c.need(n * rows * sizeof(float) + 64), DEGA_ERROR_MEMORY);
-    HIP_TRY(ctx, sl.meta.need(n * (2 * sizeof(uint64_t) + sizeof(int32_t)) + 64), DEGA_ERROR_MEMORY);
-    uint64_t *const d_len = (uint64_t *)sl.meta.p;
-    uint64_t *const d_count = d_len + n;
-    int32_t *const d_err = (int32_t *)(d_count + n);
-    HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.a.p, text + c0 * stride, stride, stride, n, in_pinned), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, rows_to_device(pl, sl.s, d_len, (const uint8_t *)(len + c0), n * sizeof(uint64_t), n * sizeof(uint64_t), 1, len_pinned),
-            DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, hipMemsetAsync(sl.c.p, 0, n * rows * sizeof(float) + 64, sl.s), DEGA_ERROR_LIBRARY_CALL); // (rows beyond a channel's count come back as +0.0f)
-    if ((ret = launch_csv_read(ctx, (const uint8_t *)sl.a.p, stride, d_len, n, column, separator_char, (float *)sl.c.p, rows, n, d_count, d_err,
-                               sl.s)) != DEGA_OK)
-      return ret;
-    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(v_tc + c0), ld * sizeof(float), sl.c.p, n * sizeof(float), rows, out_pinned), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(out_count + c0), n * sizeof(uint64_t), d_count, n * sizeof(uint64_t), 1, count_pinned),
-            DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(err + c0), n * sizeof(int32_t), d_err, n * sizeof(int32_t), 1, err_pinned), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-  return DEGA_OK;
-}

@@ -573,6 +573,38 @@ static int run_chunks(size_t nchunks, size_t ahead, Stage1 stage1, Stage2 stage2
   return DEGA_OK;
 }
 
+// The loop of the synchronous host forms: chunks of channels through the context's first slot, one after the other, as
+// many channels at a time as keep what a chunk holds on the device (bytes_per_channel each, never 0) under a gigabyte.
+// body(pl, sl, c0, n) grows the slot's buffers, uploads, launches and downloads channels [c0, c0 + n); every chunk starts
+// on an idle stream and ends with the staging ring's downloads in their place.
+template <class Body>
+static int first_slot_chunks(dega_hip_ctx *ctx, size_t C, size_t bytes_per_channel, Body body)
+{
+  int ret;
+  Pipeline *pl;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  if ((ret = pipeline_get(ctx, &pl)) != DEGA_OK)
+    return ret;
+  Slot &sl = pl->slot[0];
+  if ((ret = slot_stream(ctx, sl)) != DEGA_OK)
+    return ret;
+  size_t budget = (size_t)1 << 30;
+  if (const char *e = getenv("DEGA_HOST_CHUNK_BYTES")) // measurement / test knob: the budget in bytes, at least 1
+    budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10));
+  size_t step = std::max<size_t>(1, budget / bytes_per_channel);
+  if (step >= 4)
+    step = step / 4 * 4; // whole 16-byte units of float32 columns: the chunks' images stay on the 16-byte path
+  for (size_t c0 = 0; c0 < C; c0 += step)
+  {
+    HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+    if ((ret = body(pl, sl, c0, std::min(step, C - c0))) != DEGA_OK)
+      return ret;
+    HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
 // everything the chunks left in flight: the staging ring's downloads to their place, then the slots' streams
 static int finish_slots(dega_hip_ctx *ctx, Pipeline *pl, int nslots)
 {
@@ -2006,8 +2038,7 @@ extern "C" int dega_hip_encode_agg_job_host(dega_hip_ctx *ctx, const dega_hip_jo
   return encode_agg_on_group(&one, job, num_values, samples, packed, packed_cap, offsets, out_bits, err);
 }
 
-// float32 rows in host memory -> their sums in host memory, synchronous: chunks of channels through the context's first
-// slot (upload, one launch, download), as many channels at a time as keep the two images under a gigabyte
+// float32 rows in host memory -> their sums in host memory, synchronous (first_slot_chunks): a chunk holds the two images
 extern "C" int dega_hip_aggregate_host(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float *a_tc,
                                        size_t ld_out)
 {
@@ -2021,34 +2052,101 @@ extern "C" int dega_hip_aggregate_host(dega_hip_ctx *ctx, const float *v_tc, siz
     return DEGA_OK;
   if (v_tc == nullptr || a_tc == nullptr)
     return DEGA_ERROR_INVALID_VALUE;
-  int ret;
-  Pipeline *pl;
-  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  if ((ret = pipeline_get(ctx, &pl)) != DEGA_OK)
-    return ret;
-  Slot &sl = pl->slot[0];
-  if ((ret = slot_stream(ctx, sl)) != DEGA_OK)
-    return ret;
   const size_t T_out = dega_hip_aggregate_rows(T, num_values);
-  const size_t per_channel = (T + T_out) * sizeof(float);
-  size_t step = std::max<size_t>(1, ((size_t)1 << 30) / per_channel);
-  if (step >= 4)
-    step = step / 4 * 4; // whole 16-byte units: the chunks' images stay on the 16-byte path
   const bool in_pinned = is_pinned(v_tc), out_pinned = is_pinned(a_tc);
-  for (size_t c0 = 0; c0 < C; c0 += step)
-  {
-    const size_t n = std::min(step, C - c0);
-    HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+  return first_slot_chunks(ctx, C, (T + T_out) * sizeof(float), [&](Pipeline *pl, Slot &sl, size_t c0, size_t n) -> int {
     HIP_TRY(ctx, sl.c.need(n * T * sizeof(float) + 64), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, sl.a.need(n * T_out * sizeof(float) + 64), DEGA_ERROR_MEMORY);
     HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, (const uint8_t *)(v_tc + c0), ld * sizeof(float), n * sizeof(float), T, in_pinned), DEGA_ERROR_LIBRARY_CALL);
-    if ((ret = launch_aggregate(ctx, (const float *)sl.c.p, n, T, n, num_values, (float *)sl.a.p, n, sl.s)) != DEGA_OK)
+    const int ret = launch_aggregate(ctx, (const float *)sl.c.p, n, T, n, num_values, (float *)sl.a.p, n, sl.s);
+    if (ret != DEGA_OK)
       return ret;
     HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(a_tc + c0), ld_out * sizeof(float), sl.a.p, n * sizeof(float), T_out, out_pinned), DEGA_ERROR_LIBRARY_CALL);
-    HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
+    return DEGA_OK;
+  });
+}
+
+// float32 rows in host memory -> their text in host memory, synchronous, chunked as dega_hip_aggregate_host is: a chunk
+// holds its readings and their text
+extern "C" int dega_hip_csv_write_host(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, unsigned decimals, size_t column,
+                                       int separator_char, uint8_t *out, size_t stride, uint64_t *out_len, int32_t *err)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  if ((ret = check_csv_options(ctx, C, ld, decimals, column, separator_char, stride)) != DEGA_OK)
+    return ret;
+  if (C == 0)
+    return DEGA_OK;
+  if (out == nullptr || out_len == nullptr || err == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: out, out_len and err must be arrays", hipSuccess);
+  if (T == 0)
+  {
+    memset(out_len, 0, C * sizeof(uint64_t));
+    memset(err, 0, C * sizeof(int32_t));
+    return DEGA_OK;
   }
-  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-  return DEGA_OK;
+  if (v_tc == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv: v_tc must be a float32 array", hipSuccess);
+  const bool in_pinned = is_pinned(v_tc), out_pinned = is_pinned(out), len_pinned = is_pinned(out_len), err_pinned = is_pinned(err);
+  return first_slot_chunks(ctx, C, T * sizeof(float) + stride, [&](Pipeline *pl, Slot &sl, size_t c0, size_t n) -> int {
+    HIP_TRY(ctx, sl.c.need(n * T * sizeof(float) + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.a.need(n * stride + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.meta.need(n * (sizeof(uint64_t) + sizeof(int32_t)) + 64), DEGA_ERROR_MEMORY);
+    uint64_t *const d_len = (uint64_t *)sl.meta.p;
+    int32_t *const d_err = (int32_t *)((uint8_t *)sl.meta.p + n * sizeof(uint64_t));
+    HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, (const uint8_t *)(v_tc + c0), ld * sizeof(float), n * sizeof(float), T, in_pinned), DEGA_ERROR_LIBRARY_CALL);
+    if ((ret = launch_csv(ctx, (const float *)sl.c.p, n, T, n, decimals, column, separator_char, (uint8_t *)sl.a.p, stride, d_len, d_err, sl.s)) != DEGA_OK)
+      return ret;
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, out + c0 * stride, stride, sl.a.p, stride, n, out_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(out_len + c0), n * sizeof(uint64_t), d_len, n * sizeof(uint64_t), 1, len_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(err + c0), n * sizeof(int32_t), d_err, n * sizeof(int32_t), 1, err_pinned), DEGA_ERROR_LIBRARY_CALL);
+    return DEGA_OK;
+  });
+}
+
+// Text rows in host memory -> float32 rows in host memory, synchronous, chunked likewise: a chunk holds its text and its values
+extern "C" int dega_hip_csv_read_host(dega_hip_ctx *ctx, const uint8_t *text, size_t stride, const uint64_t *len, size_t C, size_t column,
+                                      int separator_char, float *v_tc, size_t max_T, size_t ld, uint64_t *out_count, int32_t *err)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  int ret;
+  if ((ret = check_csv_read_options(ctx, C, column, separator_char, stride, ld)) != DEGA_OK)
+    return ret;
+  if (C == 0)
+    return DEGA_OK;
+  if (text == nullptr || len == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: text and len must be arrays", hipSuccess);
+  if ((ret = check_csv_read_outputs(ctx, v_tc, max_T, out_count, err)) != DEGA_OK)
+    return ret;
+  for (size_t c = 0; c < C; c++)
+    if (len[c] > stride)
+      return fail(ctx, DEGA_ERROR_INVALID_VALUE, "csv read: a len[c] is larger than stride", hipSuccess);
+  // a text of `stride` bytes holds at most `stride` values: more room than that is never used, and sizes stay far from wrapping
+  const size_t rows = std::min(max_T, stride);
+  const bool in_pinned = is_pinned(text), len_pinned = is_pinned(len), out_pinned = is_pinned(v_tc), count_pinned = is_pinned(out_count),
+             err_pinned = is_pinned(err);
+  return first_slot_chunks(ctx, C, rows * sizeof(float) + stride, [&](Pipeline *pl, Slot &sl, size_t c0, size_t n) -> int {
+    HIP_TRY(ctx, sl.a.need(n * stride + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.c.need(n * rows * sizeof(float) + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.meta.need(n * (2 * sizeof(uint64_t) + sizeof(int32_t)) + 64), DEGA_ERROR_MEMORY);
+    uint64_t *const d_len = (uint64_t *)sl.meta.p;
+    uint64_t *const d_count = d_len + n;
+    int32_t *const d_err = (int32_t *)(d_count + n);
+    HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.a.p, text + c0 * stride, stride, stride, n, in_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_device(pl, sl.s, d_len, (const uint8_t *)(len + c0), n * sizeof(uint64_t), n * sizeof(uint64_t), 1, len_pinned),
+            DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipMemsetAsync(sl.c.p, 0, n * rows * sizeof(float) + 64, sl.s), DEGA_ERROR_LIBRARY_CALL); // (rows beyond a channel's count come back as +0.0f)
+    if ((ret = launch_csv_read(ctx, (const uint8_t *)sl.a.p, stride, d_len, n, column, separator_char, (float *)sl.c.p, rows, n, d_count, d_err,
+                               sl.s)) != DEGA_OK)
+      return ret;
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(v_tc + c0), ld * sizeof(float), sl.c.p, n * sizeof(float), rows, out_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(out_count + c0), n * sizeof(uint64_t), d_count, n * sizeof(uint64_t), 1, count_pinned),
+            DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(err + c0), n * sizeof(int32_t), d_err, n * sizeof(int32_t), 1, err_pinned), DEGA_ERROR_LIBRARY_CALL);
+    return DEGA_OK;
+  });
 }
 
 extern "C" int dega_hip_decode_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits,
@@ -2207,6 +2305,8 @@ extern "C" void dega_hip_pinned_free(void *p)
 
 // ---- LZMH, host pointers: context-owned buffers, no per-call allocation --------------------------------------------------------
 
+// Synchronous, chunked as dega_hip_aggregate_host is: a chunk holds its texts and its slabs.  Plain copies from and to the
+// caller's arrays, no staging ring.
 extern "C" int dega_hip_lzmh_encode_host(dega_hip_ctx *ctx, const uint8_t *in, size_t stride, const uint64_t *in_len, size_t C, uint8_t *out,
                                          size_t cap, uint64_t *out_bits, int32_t *err)
 {
@@ -2214,34 +2314,31 @@ extern "C" int dega_hip_lzmh_encode_host(dega_hip_ctx *ctx, const uint8_t *in, s
     return DEGA_ERROR_INVALID_VALUE;
   if (C == 0)
     return DEGA_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  Pipeline *pl;
+  if (in == nullptr || in_len == nullptr || out == nullptr || out_bits == nullptr || err == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh encode: in, in_len, out, out_bits and err must be arrays", hipSuccess);
   int ret;
-  if ((ret = pipeline_get(ctx, &pl)) != DEGA_OK)
+  if ((ret = check_lzmh_encode(ctx, stride, cap, true)) != DEGA_OK)
     return ret;
-  Slot &sl = pl->slot[0];
-  if ((ret = slot_stream(ctx, sl)) != DEGA_OK)
-    return ret;
-  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-  HIP_TRY(ctx, sl.a.need(C * stride + 64), DEGA_ERROR_MEMORY);
-  HIP_TRY(ctx, sl.b.need(C * cap + 64), DEGA_ERROR_MEMORY);
-  HIP_TRY(ctx, sl.meta.need(MetaView::bytes(C)), DEGA_ERROR_MEMORY);
-  MetaView dm(sl.meta.p, C);
-  HIP_TRY(ctx, hipMemcpyAsync(sl.a.p, in, C * stride, hipMemcpyHostToDevice, sl.s), DEGA_ERROR_LIBRARY_CALL);
-  HIP_TRY(ctx, hipMemcpyAsync(dm.counts, in_len, C * sizeof(uint64_t), hipMemcpyHostToDevice, sl.s), DEGA_ERROR_LIBRARY_CALL);
-  if ((ret = dega_hip_lzmh_encode_dev(ctx, (const uint8_t *)sl.a.p, stride, dm.counts, C, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
-    return ret;
-  HIP_TRY(ctx, hipMemcpyAsync(out_bits, dm.bits, C * sizeof(uint64_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
-  HIP_TRY(ctx, hipMemcpyAsync(err, dm.err, C * sizeof(int32_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
-  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-  // only the bytes each stream holds come back (whole 16-byte groups, as the kernel stores them)
-  uint64_t longest = 0;
-  for (size_t c = 0; c < C; c++)
-    longest = std::max(longest, std::min<uint64_t>(cap, ((out_bits[c] + 7) / 8 + 15) / 16 * 16));
-  if (longest > 0)
-    HIP_TRY(ctx, hipMemcpy2DAsync(out, cap, sl.b.p, cap, (size_t)longest, C, hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
-  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-  return DEGA_OK;
+  return first_slot_chunks(ctx, C, stride + cap, [&](Pipeline *, Slot &sl, size_t c0, size_t n) -> int {
+    HIP_TRY(ctx, sl.a.need(n * stride + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.b.need(n * cap + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.meta.need(MetaView::bytes(n)), DEGA_ERROR_MEMORY);
+    MetaView dm(sl.meta.p, n);
+    HIP_TRY(ctx, hipMemcpyAsync(sl.a.p, in + c0 * stride, n * stride, hipMemcpyHostToDevice, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipMemcpyAsync(dm.counts, in_len + c0, n * sizeof(uint64_t), hipMemcpyHostToDevice, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    if ((ret = dega_hip_lzmh_encode_dev(ctx, (const uint8_t *)sl.a.p, stride, dm.counts, n, (uint8_t *)sl.b.p, cap, dm.bits, dm.err, sl.s)) != DEGA_OK)
+      return ret;
+    HIP_TRY(ctx, hipMemcpyAsync(out_bits + c0, dm.bits, n * sizeof(uint64_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipMemcpyAsync(err + c0, dm.err, n * sizeof(int32_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+    // only the bytes each stream of the chunk holds come back (whole 16-byte groups, as the kernel stores them)
+    uint64_t longest = 0;
+    for (size_t c = c0; c < c0 + n; c++)
+      longest = std::max(longest, std::min<uint64_t>(cap, ((out_bits[c] + 7) / 8 + 15) / 16 * 16));
+    if (longest > 0)
+      HIP_TRY(ctx, hipMemcpy2DAsync(out + c0 * cap, cap, sl.b.p, cap, (size_t)longest, n, hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    return DEGA_OK;
+  });
 }
 
 extern "C" int dega_hip_lzmh_decode_host(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, uint8_t *out,
@@ -2251,28 +2348,25 @@ extern "C" int dega_hip_lzmh_decode_host(dega_hip_ctx *ctx, const uint8_t *in, s
     return DEGA_ERROR_INVALID_VALUE;
   if (C == 0)
     return DEGA_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
-  Pipeline *pl;
+  if (in == nullptr || in_bits == nullptr || out == nullptr || out_len == nullptr || err == nullptr)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "lzmh decode: in, in_bits, out, out_len and err must be arrays", hipSuccess);
   int ret;
-  if ((ret = pipeline_get(ctx, &pl)) != DEGA_OK)
+  if ((ret = check_lzmh_decode(ctx, cap, stride, true)) != DEGA_OK)
     return ret;
-  Slot &sl = pl->slot[0];
-  if ((ret = slot_stream(ctx, sl)) != DEGA_OK)
-    return ret;
-  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-  HIP_TRY(ctx, sl.a.need(C * cap + 64), DEGA_ERROR_MEMORY);
-  HIP_TRY(ctx, sl.b.need(C * stride + 64), DEGA_ERROR_MEMORY);
-  HIP_TRY(ctx, sl.meta.need(MetaView::bytes(C)), DEGA_ERROR_MEMORY);
-  MetaView dm(sl.meta.p, C);
-  HIP_TRY(ctx, hipMemcpyAsync(sl.a.p, in, C * cap, hipMemcpyHostToDevice, sl.s), DEGA_ERROR_LIBRARY_CALL);
-  HIP_TRY(ctx, hipMemcpyAsync(dm.bits, in_bits, C * sizeof(uint64_t), hipMemcpyHostToDevice, sl.s), DEGA_ERROR_LIBRARY_CALL);
-  if ((ret = dega_hip_lzmh_decode_dev(ctx, (const uint8_t *)sl.a.p, cap, dm.bits, C, (uint8_t *)sl.b.p, stride, dm.counts, dm.err, sl.s)) != DEGA_OK)
-    return ret;
-  HIP_TRY(ctx, hipMemcpyAsync(out, sl.b.p, C * stride, hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
-  HIP_TRY(ctx, hipMemcpyAsync(out_len, dm.counts, C * sizeof(uint64_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
-  HIP_TRY(ctx, hipMemcpyAsync(err, dm.err, C * sizeof(int32_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
-  HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
-  return DEGA_OK;
+  return first_slot_chunks(ctx, C, stride + cap, [&](Pipeline *, Slot &sl, size_t c0, size_t n) -> int {
+    HIP_TRY(ctx, sl.a.need(n * cap + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.b.need(n * stride + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.meta.need(MetaView::bytes(n)), DEGA_ERROR_MEMORY);
+    MetaView dm(sl.meta.p, n);
+    HIP_TRY(ctx, hipMemcpyAsync(sl.a.p, in + c0 * cap, n * cap, hipMemcpyHostToDevice, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipMemcpyAsync(dm.bits, in_bits + c0, n * sizeof(uint64_t), hipMemcpyHostToDevice, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    if ((ret = dega_hip_lzmh_decode_dev(ctx, (const uint8_t *)sl.a.p, cap, dm.bits, n, (uint8_t *)sl.b.p, stride, dm.counts, dm.err, sl.s)) != DEGA_OK)
+      return ret;
+    HIP_TRY(ctx, hipMemcpyAsync(out + c0 * stride, sl.b.p, n * stride, hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipMemcpyAsync(out_len + c0, dm.counts, n * sizeof(uint64_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipMemcpyAsync(err + c0, dm.err, n * sizeof(int32_t), hipMemcpyDeviceToHost, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    return DEGA_OK;
+  });
 }
 
 // ---- LZMH through the pipeline: chunks of channels on their own streams, packed streams out / in, and the group -----------

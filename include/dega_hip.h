@@ -215,6 +215,11 @@ int dega_hip_lzmh_decode_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, c
                              uint64_t *out_len, int32_t *err, void *stream);
 int dega_hip_lzmh_render_dev(dega_hip_ctx *ctx, const int32_t *x_tc, size_t C, size_t T, size_t ld, uint8_t *out, size_t stride,
                              uint64_t *out_len, int32_t *err, void *stream);
+/* The same for host memory, synchronous, chunked as dega_hip_aggregate_host is (a chunk holds its texts and its slabs).
+   C = 0: DEGA_OK, ahead of everything else.  Before the device is touched both refuse, with DEGA_ERROR_INVALID_VALUE and a
+   message in last_error, a null array and the stride and cap the _dev forms refuse (the alignment of the device arrays
+   is the library's own concern).  encode brings home, per chunk, as many bytes of every slab as the chunk's longest stream
+   has: what a slab holds beyond its stream's end is unspecified. */
 int dega_hip_lzmh_encode_host(dega_hip_ctx *ctx, const uint8_t *in, size_t stride, const uint64_t *in_len, size_t C, uint8_t *out, size_t cap,
                               uint64_t *out_bits, int32_t *err);
 int dega_hip_lzmh_decode_host(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, uint8_t *out, size_t stride,
@@ -255,6 +260,11 @@ int dega_hip_decode_f32_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, co
 size_t dega_hip_aggregate_rows(size_t T, size_t num_values); /* ceil(T / num_values); 0 when num_values == 0 */
 int dega_hip_aggregate_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float *a_tc, size_t ld_out,
                            void *stream);
+/* Host memory, synchronous: chunks of channels go through the context's first slot one after the other (upload, one
+   launch, download) -- as many channels at a time as keep what a chunk holds on the device, here the two images, within
+   1 GiB; at least 1, and whole fours from 4 on.  DEGA_HOST_CHUNK_BYTES=n (n >= 1; a measurement and test knob, read by
+   every call) replaces the 1 GiB.  The other synchronous host forms -- dega_hip_csv_write_host, dega_hip_csv_read_host,
+   dega_hip_lzmh_encode_host, dega_hip_lzmh_decode_host -- run the same loop. */
 int dega_hip_aggregate_host(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, size_t num_values, float *a_tc, size_t ld_out);
 /* `encode aggregate num_values=N # encode normalize # encode diff # encode seg # encode bac [adaptive]` per channel.  It
    IS dega_hip_encode_levels_f32_dev (below) with K = 1 and takes that call's path: two launches on `stream`, no
