@@ -119,6 +119,12 @@ _SIGNATURES = {
     "dega_hip_group_encode_var": (C.c_int, [_P, _P, _P, _P, _P, _Z, _P, _P, _P]),
     "dega_hip_to_time_major_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _Z, _P, _P, _Z, _P]),
     "dega_hip_to_channel_major_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _Z, _P, _P, _Z, _P]),
+    "dega_hip_axdr_bytes": (_Z, [_Z, C.c_int]),
+    "dega_hip_axdr_encode_dev": (C.c_int, [_P, _P, C.c_int, _Z, _Z, _Z, _P, C.c_float, C.c_int, _P, _Z, _P, _P, _P]),
+    "dega_hip_axdr_decode_dev": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, _Z, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "dega_hip_axdr_encode_levels_f32_dev": (C.c_int, [_P, _P, _Z, _Z, _Z, _P, _P, _Z, C.c_float, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "dega_hip_axdr_encode_host": (C.c_int, [_P, _P, C.c_int, _Z, _Z, _Z, _P, C.c_float, C.c_int, _P, _Z, _P, _P]),
+    "dega_hip_axdr_decode_host": (C.c_int, [_P, _P, _Z, _P, _Z, _Z, _Z, C.c_float, C.c_int, C.c_int, _P, _P, _P]),
     "dega_hip_profile": (C.c_int, [_P, C.c_int]),
     "dega_hip_profile_read": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int]),
 }
@@ -170,6 +176,12 @@ def worst_case_bytes(T):
 
 def lzmh_worst_case_bytes(n):
     return library().dega_hip_lzmh_worst_case_bytes(n)
+
+
+def axdr_bytes(T, valuesize):
+    """The bytes of a slab that T fields of `valuesize` bits take, 4 * ceil(T * valuesize / 32) (dega_hip_axdr_bytes; no GPU
+    needed); 0 for a value size outside 1..64."""
+    return library().dega_hip_axdr_bytes(int(T), int(valuesize))
 
 
 def csv_line_max(decimals=2, column=1):
@@ -1159,6 +1171,130 @@ class Context(_JobCalls):
                                                   lens.ctypes.data, err.ctypes.data)
         self._check(ret, "dega_hip_lzmh_decode_host")
         return out, lens, err
+
+    # ---- A-XDR: packed fields, the study's third chain ---------------------------------------------------------------
+    @staticmethod
+    def _axdr_torch_dtype(samples):
+        import torch
+        return {SAMPLES_I32: torch.int32, SAMPLES_I64: torch.int64, SAMPLES_F32: torch.float32}[samples]
+
+    def axdr_encode(self, x_tc, valuesize, factor=100.0, samples=SAMPLES_F32, count=None, channels=None, cap=None, out=None):
+        """x_tc: CUDA tensor [T, ld] of float32 readings (samples=SAMPLES_F32, valuesize 1..64), or of int32 (SAMPLES_I32, 1..32)
+        / int64 (SAMPLES_I64, 33..64) containers of fields -> every channel's A-XDR stream, one big-endian field of `valuesize`
+        bits per reading (dega_hip_axdr_encode_dev).  channels: the first `channels` columns (default all); count (int64 CUDA
+        tensor, one per channel): channel c is its first count[c] rows; cap: bytes per slab (default axdr_bytes(T, valuesize));
+        out (optional): a uint8 CUDA tensor [>= C, cap] -- only the streams' own bytes of it are written.
+        Returns (slabs uint8 [C, cap], bits int64 [C], err int32 [C])."""
+        import torch
+        assert samples in (SAMPLES_F32, SAMPLES_I32, SAMPLES_I64), "samples is SAMPLES_F32, SAMPLES_I32 or SAMPLES_I64"
+        assert x_tc.dim() == 2 and x_tc.dtype == self._axdr_torch_dtype(samples) and x_tc.is_cuda and x_tc.is_contiguous()
+        T, ld = x_tc.shape
+        Cn = ld if channels is None else int(channels)
+        assert 0 <= Cn <= ld, "channels must be at most the row pitch"
+        if out is not None:
+            assert out.dim() == 2 and out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.device == x_tc.device and out.shape[0] >= Cn
+            assert cap is None or int(cap) == out.shape[1]
+            cap = out.shape[1]
+        cap = axdr_bytes(T, valuesize) if cap is None else int(cap)
+        if out is None:
+            out = torch.zeros((Cn, cap), dtype=torch.uint8, device=x_tc.device)
+        bits = torch.zeros(Cn, dtype=torch.int64, device=x_tc.device)
+        err = torch.zeros(Cn, dtype=torch.int32, device=x_tc.device)
+        ret = library().dega_hip_axdr_encode_dev(self._h, x_tc.data_ptr(), int(samples), Cn, T, ld, None if count is None else _count_ptr(count, Cn, x_tc.device),
+                                                 float(factor), int(valuesize), out.data_ptr(), cap, bits.data_ptr(), err.data_ptr(), self._stream())
+        self._check(ret, "dega_hip_axdr_encode_dev")
+        return out[:Cn], bits, err
+
+    def axdr_decode(self, streams, bits, max_T, valuesize, factor=100.0, samples=SAMPLES_F32, ld=None, out=None):
+        """The inverse (dega_hip_axdr_decode_dev): streams uint8 CUDA tensor [C, cap], bits int64 [C] -> up to max_T fields per
+        channel as float32 (sign-extended, divided by the factor), int32 or int64 (the field, zero above it).  out
+        (optional): a tensor [>= max_T, ld >= C] of the samples' dtype, or ld: the row pitch of a new one.
+        Returns (x_tc [max_T, C], count int64 [C], err int32 [C]); rows at or beyond a channel's count are not written."""
+        import torch
+        assert samples in (SAMPLES_F32, SAMPLES_I32, SAMPLES_I64), "samples is SAMPLES_F32, SAMPLES_I32 or SAMPLES_I64"
+        assert streams.dim() == 2 and streams.dtype == torch.uint8 and streams.is_cuda and streams.is_contiguous()
+        assert bits.dtype == torch.int64 and bits.is_cuda and bits.is_contiguous() and bits.device == streams.device and bits.numel() >= streams.shape[0]
+        Cn, cap = streams.shape
+        max_T = int(max_T)
+        if out is None:
+            out = torch.zeros((max_T, Cn if ld is None else int(ld)), dtype=self._axdr_torch_dtype(samples), device=streams.device)
+        assert out.dim() == 2 and out.dtype == self._axdr_torch_dtype(samples) and out.is_cuda and out.is_contiguous() and out.device == streams.device
+        assert out.shape[0] >= max_T and out.shape[1] >= Cn and (ld is None or int(ld) == out.shape[1]), "out must hold max_T rows of at least C columns"
+        count = torch.zeros(Cn, dtype=torch.int64, device=streams.device)
+        err = torch.zeros(Cn, dtype=torch.int32, device=streams.device)
+        ret = library().dega_hip_axdr_decode_dev(self._h, streams.data_ptr(), cap, bits.data_ptr(), Cn, max_T, out.shape[1], float(factor), int(valuesize),
+                                                 int(samples), out.data_ptr(), count.data_ptr(), err.data_ptr(), self._stream())
+        self._check(ret, "dega_hip_axdr_decode_dev")
+        return out[:max_T, :Cn], count, err
+
+    def axdr_encode_levels_f32(self, v_tc, levels, valuesize, factor=100.0, count=None):
+        """axdr_encode(aggregate(v_tc, N)) for every N of `levels` from one upload (dega_hip_axdr_encode_levels_f32_dev): the
+        study's third chain at every granularity.  Returns a list of (slabs, bits, err), one per level in the order given;
+        with count (int64 CUDA tensor, one per channel: what csv_read reports) of (slabs, bits, err, counts)."""
+        import torch
+        assert v_tc.dim() == 2 and v_tc.dtype == torch.float32 and v_tc.is_cuda and v_tc.is_contiguous()
+        levels, nv = _level_array(levels)
+        K = len(levels)
+        T, Cn = v_tc.shape
+        cap = [axdr_bytes(library().dega_hip_aggregate_rows(T, n), valuesize) for n in levels]
+        out = [torch.zeros((Cn, c), dtype=torch.uint8, device=v_tc.device) for c in cap]
+        bits = [torch.zeros(Cn, dtype=torch.int64, device=v_tc.device) for _ in range(K)]
+        err = [torch.zeros(Cn, dtype=torch.int32, device=v_tc.device) for _ in range(K)]
+        counts = [torch.zeros(Cn, dtype=torch.int64, device=v_tc.device) for _ in range(K)] if count is not None else None
+        ptrs = lambda ts: (_P * max(1, K))(*[t.data_ptr() for t in ts])  # noqa: E731
+        ret = library().dega_hip_axdr_encode_levels_f32_dev(self._h, v_tc.data_ptr(), Cn, T, Cn, None if count is None else _count_ptr(count, Cn, v_tc.device), nv, K,
+                                                            float(factor), int(valuesize), ptrs(out), (_Z * max(1, K))(*cap), ptrs(bits),
+                                                            None if counts is None else ptrs(counts), ptrs(err), self._stream())
+        self._check(ret, "dega_hip_axdr_encode_levels_f32_dev")
+        return list(zip(out, bits, err)) if counts is None else list(zip(out, bits, err, counts))
+
+    def axdr_encode_host(self, x_tc, valuesize, factor=100.0, samples=SAMPLES_F32, count=None, channels=None, cap=None, out=None):
+        """axdr_encode for a numpy array [T, ld] in host memory (dega_hip_axdr_encode_host; synchronous, chunks of channels).
+        count: uint64, one per channel.  Returns (slabs uint8 [C, cap], bits uint64 [C], err int32 [C])."""
+        import numpy as np
+        assert samples in (SAMPLES_F32, SAMPLES_I32, SAMPLES_I64), "samples is SAMPLES_F32, SAMPLES_I32 or SAMPLES_I64"
+        assert isinstance(x_tc, np.ndarray) and x_tc.ndim == 2 and x_tc.flags.c_contiguous, "the samples must be a C-contiguous 2-d numpy array"
+        assert x_tc.dtype == _sample_dtype(samples), "the array's dtype must be the sample type's: nothing is converted behind the caller's back"
+        T, ld = x_tc.shape
+        Cn = ld if channels is None else int(channels)
+        assert 0 <= Cn <= ld, "channels must be at most the row pitch"
+        if count is not None:
+            count = np.ascontiguousarray(count, dtype=np.uint64)
+            assert count.size >= Cn, "one count per channel"
+        if out is not None:
+            assert isinstance(out, np.ndarray) and out.ndim == 2 and out.dtype == np.uint8 and out.flags.c_contiguous and out.shape[0] >= Cn
+            assert cap is None or int(cap) == out.shape[1]
+            cap = out.shape[1]
+        cap = axdr_bytes(T, valuesize) if cap is None else int(cap)
+        if out is None:
+            out = np.zeros((Cn, cap), dtype=np.uint8)
+        bits = np.zeros(Cn, dtype=np.uint64)
+        err = np.zeros(Cn, dtype=np.int32)
+        ret = library().dega_hip_axdr_encode_host(self._h, x_tc.ctypes.data, int(samples), Cn, T, ld, None if count is None else count.ctypes.data, float(factor),
+                                                  int(valuesize), out.ctypes.data, cap, bits.ctypes.data, err.ctypes.data)
+        self._check(ret, "dega_hip_axdr_encode_host")
+        return out[:Cn], bits, err
+
+    def axdr_decode_host(self, streams, bits, max_T, valuesize, factor=100.0, samples=SAMPLES_F32, ld=None, out=None):
+        """axdr_decode for numpy arrays in host memory (dega_hip_axdr_decode_host; synchronous, chunks of channels).
+        Returns (x_tc [max_T, C], count uint64 [C], err int32 [C])."""
+        import numpy as np
+        assert samples in (SAMPLES_F32, SAMPLES_I32, SAMPLES_I64), "samples is SAMPLES_F32, SAMPLES_I32 or SAMPLES_I64"
+        assert isinstance(streams, np.ndarray) and streams.ndim == 2 and streams.dtype == np.uint8 and streams.flags.c_contiguous
+        bits = np.ascontiguousarray(bits, dtype=np.uint64)
+        Cn, cap = streams.shape
+        assert bits.size == Cn, "one bit length per channel"
+        max_T = int(max_T)
+        if out is None:
+            out = np.zeros((max_T, Cn if ld is None else int(ld)), dtype=_sample_dtype(samples))
+        assert isinstance(out, np.ndarray) and out.ndim == 2 and out.dtype == _sample_dtype(samples) and out.flags.c_contiguous
+        assert out.shape[0] >= max_T and out.shape[1] >= Cn and (ld is None or int(ld) == out.shape[1]), "out must hold max_T rows of at least C columns"
+        count = np.zeros(Cn, dtype=np.uint64)
+        err = np.zeros(Cn, dtype=np.int32)
+        ret = library().dega_hip_axdr_decode_host(self._h, streams.ctypes.data, cap, bits.ctypes.data, Cn, max_T, out.shape[1], float(factor), int(valuesize),
+                                                  int(samples), out.ctypes.data, count.ctypes.data, err.ctypes.data)
+        self._check(ret, "dega_hip_axdr_decode_host")
+        return out[:max_T, :Cn], count, err
 
     def profile(self, enable=True):
         library().dega_hip_profile(self._h, 1 if enable else 0)

@@ -18,6 +18,7 @@
 #include "csv_read_split_kernels.hpp"
 #include "csv_write_split_kernels.hpp"
 #include "transpose_kernels.hpp"
+#include "axdr_kernels.hpp"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1065,6 +1066,156 @@ extern "C" int dega_hip_encode_levels_f32_var_dev(dega_hip_ctx *ctx, const float
                                                   const size_t *cap, uint64_t *const *out_bits, uint64_t *const *out_count, int32_t *const *err, void *stream)
 {
   return encode_levels(ctx, v_tc, C, T, ld, true, count, num_values, K, factor, adaptive, valuesize, out, cap, out_bits, out_count, err, (hipStream_t)stream);
+}
+
+// ---- A-XDR: packed fields (axdr_kernels.hpp), the study's third chain ----------------------------------------------------------
+
+extern "C" size_t dega_hip_axdr_bytes(size_t T, int valuesize)
+{
+  size_t bits;
+  if (valuesize < 1 || valuesize > 64 || __builtin_mul_overflow(T, (size_t)valuesize, &bits) || bits > ~(size_t)0 - 31)
+    return 0;
+  return (bits + 31) / 32 * 4;
+}
+
+// What every A-XDR entry point refuses before the device is touched, the host forms included.  rows: T or max_T; x_tc: the
+// rows; slabs, bits, err: the per-channel arrays of either direction; counts: `count` (may be null) or `out_count` (may not).
+static int check_axdr(dega_hip_ctx *ctx, int samples, int valuesize, size_t C, size_t rows, size_t ld, size_t cap, const void *x_tc, const void *slabs,
+                      const void *bits, const void *err, const void *counts, bool counts_needed)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (samples != DEGA_SAMPLES_F32 && samples != DEGA_SAMPLES_I32 && samples != DEGA_SAMPLES_I64)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "axdr: samples must be DEGA_SAMPLES_F32, _I32 or _I64, time-major", hipSuccess);
+  if (valuesize < 1 || valuesize > 64 || (samples == DEGA_SAMPLES_I32 && valuesize > 32) || (samples == DEGA_SAMPLES_I64 && valuesize <= 32))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "axdr: sample type and valuesize do not go together (int32: 1..32, int64: 33..64, float32: 1..64)", hipSuccess);
+  if (ld < C)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "axdr: ld < C", hipSuccess);
+  size_t all;
+  if (cap % 4 != 0 || __builtin_mul_overflow(C, cap, &all))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "axdr: cap must be a multiple of 4, and C * cap fit the address space", hipSuccess);
+  if (rows > AX_MAX_T)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "axdr: at most 2^32 - 1 rows", hipSuccess);
+  if (C == 0)
+    return DEGA_OK;
+  const uintptr_t esz = samples == DEGA_SAMPLES_I64 ? 8 : 4;
+  if ((x_tc == nullptr && rows != 0) || ((uintptr_t)x_tc & (esz - 1)) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "axdr: the rows must be an array aligned to its elements", hipSuccess);
+  if ((slabs == nullptr && cap != 0) || ((uintptr_t)slabs & 3u) != 0 || bits == nullptr || ((uintptr_t)bits & 7u) != 0 || err == nullptr ||
+      ((uintptr_t)err & 3u) != 0 || (counts == nullptr && counts_needed) || ((uintptr_t)counts & 7u) != 0)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "axdr: the slabs (4-byte aligned), the bit lengths and counts (8) and err (4) must be arrays", hipSuccess);
+  return DEGA_OK;
+}
+
+static uint32_t axdr_kind(int samples)
+{
+  return samples == DEGA_SAMPLES_F32 ? AX_F32 : (samples == DEGA_SAMPLES_I32 ? AX_I32 : AX_I64);
+}
+
+// The status zeroed and the pack kernel behind it on s; the arguments have been through check_axdr, and C is not 0
+static int launch_axdr_pack(dega_hip_ctx *ctx, const void *x_tc, int samples, size_t C, size_t T, size_t ld, const uint64_t *count, float factor, int valuesize,
+                            uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, hipStream_t s)
+{
+  HIP_TRY(ctx, hipMemsetAsync(err, 0, C * sizeof(int32_t), s), DEGA_ERROR_LIBRARY_CALL);
+  if (!launch(axdr_variant(axdr_kind(samples), valuesize, x_tc, ld), axdr_pack_args(x_tc, C, T, ld, count, factor, valuesize, out, cap, out_bits, err), TR_GRID_X,
+              OnStream{s}))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "axdr encode: too many tiles for one launch", hipSuccess);
+  HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
+static int launch_axdr_unpack(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t max_T, size_t ld, float factor,
+                              int valuesize, int samples, void *x_tc, uint64_t *out_count, int32_t *err, hipStream_t s)
+{
+  if (!launch(axdr_variant(axdr_kind(samples), valuesize, x_tc, ld), axdr_unpack_args(in, cap, in_bits, C, max_T, ld, factor, valuesize, x_tc, out_count, err),
+              TR_GRID_X, OnStream{s}))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "axdr decode: too many tiles for one launch", hipSuccess);
+  HIP_TRY(ctx, hipGetLastError(), DEGA_ERROR_LIBRARY_CALL);
+  return DEGA_OK;
+}
+
+extern "C" int dega_hip_axdr_encode_dev(dega_hip_ctx *ctx, const void *x_tc, int samples, size_t C, size_t T, size_t ld, const uint64_t *count, float factor,
+                                        int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream)
+{
+  int ret;
+  if ((ret = check_axdr(ctx, samples, valuesize, C, T, ld, cap, x_tc, out, out_bits, err, count, false)) != DEGA_OK || C == 0)
+    return ret;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  return launch_axdr_pack(ctx, x_tc, samples, C, T, ld, count, factor, valuesize, out, cap, out_bits, err, (hipStream_t)stream);
+}
+
+extern "C" int dega_hip_axdr_decode_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t max_T, size_t ld,
+                                        float factor, int valuesize, int samples, void *x_tc, uint64_t *out_count, int32_t *err, void *stream)
+{
+  int ret;
+  if ((ret = check_axdr(ctx, samples, valuesize, C, max_T, ld, cap, x_tc, in, in_bits, err, out_count, true)) != DEGA_OK || C == 0)
+    return ret;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  return launch_axdr_unpack(ctx, in, cap, in_bits, C, max_T, ld, factor, valuesize, samples, x_tc, out_count, err, (hipStream_t)stream);
+}
+
+// encode_levels with the pack kernel in the coder's place: aggregate into the context's scratch, then one pack per level.
+// A null `count` is the uniform form (out_count is not looked at then).
+extern "C" int dega_hip_axdr_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
+                                                   const size_t *num_values, size_t K, float factor, int valuesize, uint8_t *const *out, const size_t *cap,
+                                                   uint64_t *const *out_bits, uint64_t *const *out_count, int32_t *const *err, void *stream)
+{
+  if (ctx == nullptr)
+    return DEGA_ERROR_INVALID_VALUE;
+  if (check_level_list(num_values, K) != DEGA_OK)
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "axdr levels: at most 8 levels, every num_values at least 1, none twice", hipSuccess);
+  if (K == 0)
+    return DEGA_OK;
+  const bool counted = count != nullptr;
+  if (out == nullptr || cap == nullptr || out_bits == nullptr || err == nullptr || (counted && out_count == nullptr))
+    return fail(ctx, DEGA_ERROR_INVALID_VALUE, "axdr levels: out, cap, out_bits, err (and out_count with count) are arrays of K entries", hipSuccess);
+  int ret;
+  size_t rows[AGG_MAX_LEVELS];
+  for (size_t k = 0; k < K; k++) // every level's pack judged before the first launch
+  {
+    rows[k] = dega_hip_aggregate_rows(T, num_values[k]);
+    if ((ret = check_axdr(ctx, DEGA_SAMPLES_F32, valuesize, C, rows[k], ld, cap[k], v_tc, out[k], out_bits[k], err[k], counted ? out_count[k] : nullptr,
+                          counted)) != DEGA_OK)
+      return ret;
+  }
+  LevelSums sums(num_values, K, T, ld, false);
+  if (C == 0)
+    return DEGA_OK;
+  if (counted && (ret = check_counts(ctx, C, T, count, out_count, K, err[0])) != DEGA_OK)
+    return ret;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(ctx, hipSetDevice(ctx->device), DEGA_ERROR_LIBRARY_CALL);
+  const size_t head = counted ? round4(C) : 0; // a counted batch: the summed levels' common status (a count above T) in front of their sums
+  if ((ret = scratch_acquire(ctx, ctx->sums, (head + std::max<size_t>(sums.floats, 4)) * sizeof(float), s)) != DEGA_OK)
+    return ret;
+  int32_t *const first = counted ? (int32_t *)ctx->sums.p : nullptr;
+  sums.place((float *)ctx->sums.p + head);
+  if ((ret = check_levels_dev(ctx, v_tc, C, T, ld, sums.N, sums.n, sums.a, sums.ldo)) != DEGA_OK)
+    return ret;
+  uint64_t *oc[AGG_MAX_LEVELS];
+  for (size_t i = 0; i < sums.n && counted; i++)
+    oc[i] = out_count[sums.level[i]];
+  if ((ret = launch_aggregate_levels(ctx, v_tc, C, T, ld, count, sums.N, sums.n, sums.a, sums.ldo, oc, first, s)) == DEGA_OK)
+  {
+    size_t i = 0;
+    for (size_t k = 0; k < K && ret == DEGA_OK; k++)
+    {
+      if (num_values[k] == 1) // packed from the readings, with `count` itself
+      {
+        if (counted)
+          hipLaunchKernelGGL(dega_level_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, count, C, T, out_count[k]);
+        ret = launch_axdr_pack(ctx, v_tc, DEGA_SAMPLES_F32, C, T, ld, count, factor, valuesize, out[k], cap[k], out_bits[k], err[k], s);
+        continue;
+      }
+      // (counted: a channel whose count is above T has level counts of 0: it is packed as empty, and the status launch names it)
+      ret = launch_axdr_pack(ctx, sums.a[i++], DEGA_SAMPLES_F32, C, rows[k], ld, counted ? out_count[k] : nullptr, factor, valuesize, out[k], cap[k],
+                             out_bits[k], err[k], s);
+      if (counted && ret == DEGA_OK)
+        ret = launch_status(ctx, first, C, err[k], out_bits[k], s);
+    }
+  }
+  const int rel = scratch_release(ctx, ctx->sums, s);
+  return rel != DEGA_OK ? rel : ret;
 }
 
 // exclusive prefix sum of ceil(bits/8) over channels: one block, chunked (C is at most a few million; not a hot path)

@@ -2149,6 +2149,82 @@ extern "C" int dega_hip_csv_read_host(dega_hip_ctx *ctx, const uint8_t *text, si
   });
 }
 
+// Rows in host memory -> their A-XDR streams in host slabs, synchronous, chunked likewise: a chunk holds its rows and its
+// slabs.  Of a slab only the stream's own bytes come back (the bytes behind them are the caller's): the chunk's bit lengths
+// and statuses first, then one 2-D copy per run of channels whose streams are equally long -- one, for a uniform batch.
+extern "C" int dega_hip_axdr_encode_host(dega_hip_ctx *ctx, const void *x_tc, int samples, size_t C, size_t T, size_t ld, const uint64_t *count, float factor,
+                                         int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err)
+{
+  int ret;
+  if ((ret = check_axdr(ctx, samples, valuesize, C, T, ld, cap, x_tc, out, out_bits, err, count, false)) != DEGA_OK || C == 0)
+    return ret;
+  const size_t esz = samples == DEGA_SAMPLES_I64 ? 8 : 4;
+  const bool in_pinned = is_pinned(x_tc), count_pinned = is_pinned(count), bits_pinned = is_pinned(out_bits), err_pinned = is_pinned(err);
+  return first_slot_chunks(ctx, C, T * esz + cap + 16, [&](Pipeline *pl, Slot &sl, size_t c0, size_t n) -> int {
+    HIP_TRY(ctx, sl.c.need(n * T * esz + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.b.need(n * cap + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.meta.need(MetaView::bytes(n)), DEGA_ERROR_MEMORY);
+    MetaView dm(sl.meta.p, n);
+    HIP_TRY(ctx, rows_to_device(pl, sl.s, sl.c.p, (const uint8_t *)x_tc + c0 * esz, ld * esz, n * esz, T, in_pinned), DEGA_ERROR_LIBRARY_CALL);
+    if (count != nullptr)
+      HIP_TRY(ctx, rows_to_device(pl, sl.s, dm.counts, (const uint8_t *)(count + c0), n * sizeof(uint64_t), n * sizeof(uint64_t), 1, count_pinned),
+              DEGA_ERROR_LIBRARY_CALL);
+    if ((ret = launch_axdr_pack(ctx, sl.c.p, samples, n, T, n, count != nullptr ? dm.counts : nullptr, factor, valuesize, (uint8_t *)sl.b.p, cap, dm.bits, dm.err,
+                                sl.s)) != DEGA_OK)
+      return ret;
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(out_bits + c0), n * sizeof(uint64_t), dm.bits, n * sizeof(uint64_t), 1, bits_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(err + c0), n * sizeof(int32_t), dm.err, n * sizeof(int32_t), 1, err_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipStreamSynchronize(sl.s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, pl->stager.drain(), DEGA_ERROR_LIBRARY_CALL);
+    auto bytes_of = [&](size_t c) -> size_t { return err[c] == DEGA_OK ? (size_t)((out_bits[c] + 31) / 32 * 4) : 0; };
+    for (size_t i = 0; i < n;)
+    {
+      const size_t len = bytes_of(c0 + i);
+      size_t k = i + 1;
+      while (k < n && bytes_of(c0 + k) == len)
+        k++;
+      if (len != 0)
+        HIP_TRY(ctx, hipMemcpy2DAsync(out + (c0 + i) * cap, cap, (const uint8_t *)sl.b.p + i * cap, cap, len, k - i, hipMemcpyDeviceToHost, sl.s),
+                DEGA_ERROR_LIBRARY_CALL);
+      i = k;
+    }
+    return DEGA_OK;
+  });
+}
+
+// A-XDR streams in host slabs -> rows in host memory, synchronous, chunked likewise.  Of a slab the bytes up to the longest
+// stream of the chunk go up; the rows come back whole (those behind a channel's count as +0 / 0).
+extern "C" int dega_hip_axdr_decode_host(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t max_T, size_t ld,
+                                         float factor, int valuesize, int samples, void *x_tc, uint64_t *out_count, int32_t *err)
+{
+  int ret;
+  if ((ret = check_axdr(ctx, samples, valuesize, C, max_T, ld, cap, x_tc, in, in_bits, err, out_count, true)) != DEGA_OK || C == 0)
+    return ret;
+  const size_t esz = samples == DEGA_SAMPLES_I64 ? 8 : 4;
+  const bool bits_pinned = is_pinned(in_bits), out_pinned = is_pinned(x_tc), count_pinned = is_pinned(out_count), err_pinned = is_pinned(err);
+  return first_slot_chunks(ctx, C, max_T * esz + cap + 16, [&](Pipeline *pl, Slot &sl, size_t c0, size_t n) -> int {
+    HIP_TRY(ctx, sl.a.need(n * cap + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.c.need(n * max_T * esz + 64), DEGA_ERROR_MEMORY);
+    HIP_TRY(ctx, sl.meta.need(MetaView::bytes(n)), DEGA_ERROR_MEMORY);
+    MetaView dm(sl.meta.p, n);
+    uint64_t longest = 0;
+    for (size_t c = c0; c < c0 + n; c++)
+      longest = std::max(longest, std::min<uint64_t>(cap, (in_bits[c] + 31) / 32 * 4));
+    if (longest > 0)
+      HIP_TRY(ctx, hipMemcpy2DAsync(sl.a.p, cap, in + c0 * cap, cap, (size_t)longest, n, hipMemcpyHostToDevice, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_device(pl, sl.s, dm.bits, (const uint8_t *)(in_bits + c0), n * sizeof(uint64_t), n * sizeof(uint64_t), 1, bits_pinned),
+            DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, hipMemsetAsync(sl.c.p, 0, n * max_T * esz + 64, sl.s), DEGA_ERROR_LIBRARY_CALL);
+    if ((ret = launch_axdr_unpack(ctx, (const uint8_t *)sl.a.p, cap, dm.bits, n, max_T, n, factor, valuesize, samples, sl.c.p, dm.counts, dm.err, sl.s)) != DEGA_OK)
+      return ret;
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)x_tc + c0 * esz, ld * esz, sl.c.p, n * esz, max_T, out_pinned), DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(out_count + c0), n * sizeof(uint64_t), dm.counts, n * sizeof(uint64_t), 1, count_pinned),
+            DEGA_ERROR_LIBRARY_CALL);
+    HIP_TRY(ctx, rows_to_host(pl, sl.s, (uint8_t *)(err + c0), n * sizeof(int32_t), dm.err, n * sizeof(int32_t), 1, err_pinned), DEGA_ERROR_LIBRARY_CALL);
+    return DEGA_OK;
+  });
+}
+
 extern "C" int dega_hip_decode_job_host(dega_hip_ctx *ctx, const dega_hip_job *job, const uint8_t *packed, const uint64_t *offsets, const uint64_t *in_bits,
                                         void *samples, uint64_t *out_count, int32_t *err)
 {

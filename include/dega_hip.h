@@ -545,6 +545,59 @@ int dega_hip_to_time_major_dev(dega_hip_ctx *ctx, const void *x_ct, size_t C, si
 int dega_hip_to_channel_major_dev(dega_hip_ctx *ctx, const void *x_tc, size_t C, size_t T, size_t ld, size_t elem_bytes, const uint64_t *count,
                                   void *x_ct, size_t stride, void *stream);
 
+/* ---- A-XDR: packed fields, the reference's third coding (`decode csv # encode normalize`) ---------------------------------- */
+/* Every reading of a channel as one big-endian two's-complement field of `valuesize` bits, packed MSB first, what Normalize
+   writes and Denormalize reads (DCLib/src/normalize.c:9-41), in the container of the DEGA streams: uint8 [C][cap] slabs of
+   big-endian 32-bit words, the exact bit length per channel.  Rows are time-major [T][ld]; samples is DEGA_SAMPLES_F32
+   (valuesize 1..64; `factor` matters for it alone), DEGA_SAMPLES_I32 (1..32) or DEGA_SAMPLES_I64 (33..64): integer rows
+   hold fields in their low valuesize bits -- what lies above is ignored on the way in and zero on the way out.
+
+   dega_hip_axdr_bytes: 4 * ceil(T * valuesize / 32), the bytes of a slab that T fields take; 0 for T = 0, a valuesize outside
+   1..64, or a product that does not fit size_t.
+
+   encode, per channel, with n = count ? count[c] : T (count: device uint64 [C], may be NULL): out_bits[c] = n * valuesize,
+   the slab's first dega_hip_axdr_bytes(n, valuesize) bytes hold the stream, zero padded to the word, and no other byte of
+   the slab is written.  err[c] = DEGA_ERROR_INVALID_VALUE if a reading among the first n fails the range check of
+   normalize.c:21 -- the reference stops there, so bits and bytes of that channel are then not defined, but nothing outside
+   its dega_hip_axdr_bytes(T, valuesize) bytes is written.  NaNs, infinities and subnormals: as dega_hip_normalize_dev.  Rows
+   at or behind n may be loaded but influence nothing.  count[c] > T: DEGA_ERROR_INVALID_VALUE and 0 bits; a stream that does
+   not fit cap: DEGA_ERROR_MEMORY and 0 bits; both with nothing written and the neighbours untouched.  out_bits feeds
+   dega_hip_compact_offsets_dev / _gather_dev as it is.
+
+   decode, per channel: out_count[c] = in_bits[c] / valuesize fields go to rows 0 .. of column c -- floats sign-extended and
+   divided by the factor, integers with zero above the field; err[c] = 0, or DEGA_ERROR_LIBRARY_CALL (-11, what the
+   reference's reader answers to a stream that ends inside a field) where in_bits[c] is no multiple of valuesize,
+   DEGA_ERROR_MEMORY where the count is above max_T (out_count[c] = the room needed), DEGA_ERROR_INVALID_VALUE where
+   in_bits[c] > 8 * cap.  Not defined, by the convention of dega_hip_decode_var_dev: rows at or beyond a channel's count, and
+   the column of a channel with err != 0.  Nothing outside the C columns and max_T rows is written, and no bit at or beyond
+   in_bits[c] influences anything.
+
+   Refused with DEGA_ERROR_INVALID_VALUE before the device is touched, by the host forms too: a null context;
+   DEGA_SAMPLES_BE32, DEGA_SAMPLES_CHANNEL_MAJOR or an unknown sample type; a valuesize that does not go with it; ld < C; a
+   cap that is no multiple of 4; more than 2^32 - 1 rows; null or misaligned arrays (C != 0).  C = 0: DEGA_OK.  The _dev
+   forms enqueue a memset of err and one kernel (decode: one kernel) on `stream` without synchronising.
+
+   dega_hip_axdr_encode_levels_f32_dev: the study's third chain, `decode csv # encode aggregate # encode normalize`, for up to
+   DEGA_AGG_MAX_LEVELS granularities from one upload -- dega_hip_encode_levels_f32_dev with the pack in the coder's place
+   (aggregate into the context's scratch, then one pack per level; num_values 1 packs v_tc itself).  count NULL: the uniform
+   form, out_count is not looked at; else the counts that dega_hip_csv_read_dev reports, and out_count[k][c] =
+   ceil(count[c] / num_values[k]).
+
+   The host forms take host pointers, are synchronous and run chunks of channels through the context's first slot (the budget
+   of a chunk: DEGA_HOST_CHUNK_BYTES); of a slab only the stream's own bytes come back. */
+size_t dega_hip_axdr_bytes(size_t T, int valuesize);
+int dega_hip_axdr_encode_dev(dega_hip_ctx *ctx, const void *x_tc, int samples, size_t C, size_t T, size_t ld, const uint64_t *count, float factor,
+                             int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err, void *stream);
+int dega_hip_axdr_decode_dev(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t max_T, size_t ld, float factor,
+                             int valuesize, int samples, void *x_tc, uint64_t *out_count, int32_t *err, void *stream);
+int dega_hip_axdr_encode_levels_f32_dev(dega_hip_ctx *ctx, const float *v_tc, size_t C, size_t T, size_t ld, const uint64_t *count,
+                                        const size_t *num_values, size_t K, float factor, int valuesize, uint8_t *const *out, const size_t *cap,
+                                        uint64_t *const *out_bits, uint64_t *const *out_count, int32_t *const *err, void *stream);
+int dega_hip_axdr_encode_host(dega_hip_ctx *ctx, const void *x_tc, int samples, size_t C, size_t T, size_t ld, const uint64_t *count, float factor,
+                              int valuesize, uint8_t *out, size_t cap, uint64_t *out_bits, int32_t *err);
+int dega_hip_axdr_decode_host(dega_hip_ctx *ctx, const uint8_t *in, size_t cap, const uint64_t *in_bits, size_t C, size_t max_T, size_t ld, float factor,
+                              int valuesize, int samples, void *x_tc, uint64_t *out_count, int32_t *err);
+
 /* ---- host pointers: the pipelined path DCCLI's stage loop (DCCLI/src/cli.c:430-466) ends up on ---------------------------- */
 /* `samples` and the outputs are HOST memory (pageable or pinned).  The batch is cut into chunks of channels, each on a
    stream of its own: upload of its columns, kernels, packing, download of its stream bytes -- copies and kernels of
